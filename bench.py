@@ -10,12 +10,20 @@ duplicate_factor 5 and static MLM masking (CPython-exact `random` replay per par
 the device-resident sample table (A/B token ids, num_tokens, is_random_next, masked positions and
 labels). Every step recomputes everything from the text; nothing is cached between steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run sets up, runs W untimed and K timed steps and prints the headline line (value,
+ms_per_step, the stage times and rooflines that the timed steps' own events give). `--full` adds
+every line that takes runs of its own: the other RNG mode (alt_rng), the raw-document input
+(with_segmentation), the PCIe-inclusive and reference-partitioning lines, the CPU baseline and,
+at N > 1, c4_exchange; the `--no-*` options drop single lines from a `--full` run.
+`--dump-outputs DIR` writes what the last timed step returned (a seeded sample of its PairBatch
+plus whole-array counts and sums, see dump_outputs) as DIR/<name>.npy.
 
 Multi-GPU: documents are sharded across ranks (each rank owns disjoint documents of the corpus and
 its own partitions); the path has no data-path collective for C2, so `scaling` is "weak". At N > 1
-the line also carries `c4_exchange`: one C4-style step per rank (seq 512, 64 bins, 8 x N shards)
+the line of a `--full` run also carries `c4_exchange`: one C4-style step per rank (seq 512, 64 bins, 8 x N shards)
 through the load balance, i.e. the RCCL bin-count all-gather and all-to-all-v exchange.
 value = sum over ranks of output tokens (sum of num_tokens, [CLS]/[SEP] included) / max rank time.
 """
@@ -115,6 +123,77 @@ def partition_prefix(corp, part, max_bytes):
     doc_b = corp.sent_off[corp.doc_sent_off[part]]  # text byte at each partition boundary
     p1 = int(np.searchsorted(doc_b, doc_b[0] + max_bytes, 'right')) - 1
     return int(min(max(p1, 1), len(part) - 1))
+
+
+def _device_sum(t, unsigned16=False, block=1 << 28):
+    """Exact integer sum of a device tensor, block by block (no whole-array temporaries).
+    unsigned16: int16 storage that holds uint16 values (ids, positions)."""
+    s = torch.zeros((), dtype=torch.int64, device=t.device)
+    for i in range(0, t.numel(), block):
+        x = t[i:i + block]
+        s += x.sum(dtype=torch.int64)
+        if unsigned16 and x.dtype == torch.int16:
+            s += 65536 * (x < 0).sum(dtype=torch.int64)
+    return float(s.item())
+
+
+def _ragged_gather(values, off, q):
+    """values[off[q[i]]:off[q[i] + 1]] for every i, concatenated (device tensors). Plain slices:
+    `values` may hold more than 2^32 elements."""
+    a0 = off.index_select(0, q).tolist()
+    a1 = off.index_select(0, q + 1).tolist()
+    if not a0:
+        return values[:0]
+    return torch.cat([values[a:b] for a, b in zip(a0, a1)])
+
+
+def dump_outputs(path, pbs, seed, rank, world, n_sample=32768):
+    """--dump-outputs: what the last timed step returned, as float32 / float64 .npy files of
+    about 25 MB in all. Per PairBatch (one, or one per chunk with --chunks; `chunk<k>_` prefix
+    then, `_rank<r>` suffix at N > 1):
+      counts          [pairs, A/B tokens, masks, kept sentences, kept documents]
+      sums            exact whole-array sums of [tokens, len_a, is_random_next, pos, labels]
+      part_off        the pair range of every partition (whole array)
+      sample_pair     n_sample pair indices drawn without replacement by
+                      numpy.random.default_rng(seed), ascending; of those pairs:
+      sample_tok_off, sample_len_a, sample_is_random_next, sample_num_tokens, sample_pos_off,
+      sample_num_masked   one value per pair
+      sample_tokens, sample_pos, sample_labels   the pairs' token ids, masked positions and
+                      labels, concatenated in sample order
+    Ids, positions and per-pair counts are exact in float32, offsets and sums in float64."""
+    os.makedirs(path, exist_ok=True)
+    sfx = '' if world == 1 else '_rank{}'.format(rank)
+    rng = np.random.default_rng(seed)
+
+    def save(name, a, dtype):
+        a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if a.dtype == np.int16:  # uint16 ids / positions in int16 storage
+            a = a.view(np.uint16)
+        np.save(os.path.join(path, name + sfx + '.npy'), a.astype(dtype))
+
+    for c, pb in enumerate(pbs):
+        pre = '' if len(pbs) == 1 else 'chunk{}_'.format(c)
+        n = pb.n_pairs
+        save(pre + 'counts', [n, pb.tokens.numel(), pb.n_masked, pb.n_kept_sentences,
+                              pb.n_kept_documents], np.float64)
+        save(pre + 'sums', [_device_sum(pb.tokens, True), _device_sum(pb.len_a),
+                            _device_sum(pb.is_random_next), _device_sum(pb.pos, True),
+                            _device_sum(pb.labels, True)], np.float64)
+        save(pre + 'part_off', pb.part_off, np.float64)
+        k = min(n, max(1, n_sample // len(pbs)))
+        qs = np.sort(rng.choice(n, size=k, replace=False)) if n else np.zeros(0, np.int64)
+        q = torch.from_numpy(qs.astype(np.int64)).to(pb.tok_off.device)
+        save(pre + 'sample_pair', qs, np.float64)
+        t0, p0 = pb.tok_off.index_select(0, q), pb.pos_off.index_select(0, q)
+        save(pre + 'sample_tok_off', t0, np.float64)
+        save(pre + 'sample_num_tokens', pb.tok_off.index_select(0, q + 1) - t0 + 3, np.float32)
+        save(pre + 'sample_len_a', pb.len_a.index_select(0, q), np.float32)
+        save(pre + 'sample_is_random_next', pb.is_random_next.index_select(0, q), np.float32)
+        save(pre + 'sample_pos_off', p0, np.float64)
+        save(pre + 'sample_num_masked', pb.pos_off.index_select(0, q + 1) - p0, np.float32)
+        save(pre + 'sample_tokens', _ragged_gather(pb.tokens, pb.tok_off, q), np.float32)
+        save(pre + 'sample_pos', _ragged_gather(pb.pos, pb.pos_off, q), np.float32)
+        save(pre + 'sample_labels', _ragged_gather(pb.labels, pb.pos_off, q), np.float32)
 
 
 def c4_exchange(args, ctx, dev, corp, part, seeds, text, world):
@@ -735,7 +814,21 @@ def main():
     ap.add_argument('--rng', choices=['replay', 'native'], default='replay',
                     help='replay: CPython MT19937 per partition, bit-exact with the reference; '
                          'native: Philox counter RNG, documents and pairs in parallel')
+    ap.add_argument('--full', action='store_true',
+                    help='c2/c3/c4: also run every line that takes runs of its own (alt_rng, '
+                         'with_segmentation, pcie_inclusive, ref_partitioning, cpu_baseline, '
+                         'c4_exchange at N > 1); the --no-* options drop single ones')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='c2: write what the last timed step returned (seeded sample of its '
+                         'PairBatch + whole-array counts and sums) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.workload != 'c2':
+        ap.error('--dump-outputs is implemented for --workload c2')
+    if not args.full:  # a plain run: only what the headline line needs
+        args.alt_rng = args.extra_lines = args.segmented_line = args.exchange_line = False
+        args.no_cpu_baseline = True
     if args.steps is None:
         args.steps = 200 if args.workload == 'c5' else 5
     if args.warmup is None:
@@ -809,11 +902,12 @@ def main():
                 ev.append([torch.cuda.Event(enable_timing=True) for _ in range(3)])
             ev[-1][i].record()
 
-    def step(ev=None, rng=args.rng, b=None):
-        """ev: list that collects one (start, tokenized, paired) event triple per (sub-)batch."""
+    def step(ev=None, rng=args.rng, b=None, keep=None):
+        """ev: list that collects one (start, tokenized, paired) event triple per (sub-)batch.
+        keep: list that receives the step's PairBatch(es) instead of their being dropped (c2)."""
         b = base if b is None else b
         if args.chunks > 1 and args.workload == 'c2':
-            return step_chunked(ev, rng, b)
+            return step_chunked(ev, rng, b, keep)
         sb = None
         if stream:
             from lddl_amd.balance import StreamBalancer
@@ -851,13 +945,15 @@ def main():
                            ('tokens', n), ('kept_sent', pb.n_kept_sentences),
                            ('kept_doc', pb.n_kept_documents)):
                 st[k_] += v_
+            if keep is not None:
+                keep.append(pb)
             del pb  # nothing of a step outlives it (HBM is reused by the next step)
         if sb is not None:
             st['shard_counts_spread'] = int((sb.all_shard_counts.max(0) -
                                              sb.all_shard_counts.min(0)).max())
         return n_tok, st, sent_lens
 
-    def step_chunked(ev, rng, b):
+    def step_chunked(ev, rng, b, keep=None):
         """The same step with tokenization of chunk k+1 pipelined under the pairs of chunk k
         (lddl_amd.pairs.tokenize_and_pair_chunked); tokenize_ms then spans only chunk 0."""
         from lddl_amd.pairs import tokenize_and_pair_chunked
@@ -873,14 +969,17 @@ def main():
               'plan_ms': sum(p.plan_ms for p in pbs), 'tokens': n_tok,
               'kept_sent': sum(p.n_kept_sentences for p in pbs),
               'kept_doc': sum(p.n_kept_documents for p in pbs)}
+        if keep is not None:
+            keep.extend(pbs)
         del pbs
         return n_tok, st, None
 
-    def timed(rng, b=None, pcie=None):
+    def timed(rng, b=None, pcie=None, keep=None):
         """W untimed steps, then exactly K steps between barrier + synchronize; max over ranks.
         pcie: host-resident mode — every step first copies its text + sentence offsets from
         pinned host memory (H2D on a copy stream, double-buffered: step k+1's copy overlaps step
-        k's compute); the timed region holds all K copies."""
+        k's compute); the timed region holds all K copies. keep: list that receives the last
+        timed step's PairBatch(es) (--dump-outputs)."""
         for _ in range(args.warmup):
             step(rng=rng, b=b)
         torch.cuda.synchronize()
@@ -899,7 +998,8 @@ def main():
                 bk = pcie['wait'](k)
                 if k + 1 < args.steps:
                     pcie['issue'](k + 1)
-            n, st, sent_len = step(evs[k], rng=rng, b=bk if pcie is not None else b)
+            n, st, sent_len = step(evs[k], rng=rng, b=bk if pcie is not None else b,
+                                   keep=keep if k == args.steps - 1 else None)
             if pcie is not None:
                 pcie['release'](k)
             out_tokens += n
@@ -917,8 +1017,12 @@ def main():
             out_tokens = int(n.item())
         return dt, out_tokens, evs, stats, sent_len
 
-    dt, out_tokens, evs, stats, sent_len = timed(args.rng)
+    kept = [] if args.dump_outputs else None
+    dt, out_tokens, evs, stats, sent_len = timed(args.rng, keep=kept)
     mem_head = torch.cuda.memory_stats()  # the headline's own allocator record
+    if kept is not None:
+        dump_outputs(args.dump_outputs, kept, args.seed, rank, world)
+        del kept[:]
     pcie_line = ref_part = None
     if world == 1 and args.workload == 'c2' and args.extra_lines:
         torch.cuda.empty_cache()  # (between lines, untimed) each line starts from an empty pool

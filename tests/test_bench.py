@@ -75,6 +75,93 @@ def test_partition_prefix():
     assert bench.partition_prefix(corp, part, 10 ** 9) == 10
 
 
+def test_dump_outputs_sample_of_a_pair_batch(tmp_path):
+    """--dump-outputs: counts, exact sums (uint16 ids in int16 storage), the partition offsets and
+    a seeded sample of pairs with their ragged token / position / label rows, the same files for
+    the same seed."""
+    import numpy as np
+    import torch
+    from lddl_amd.pairs import PairBatch
+    g = np.random.default_rng(7)
+    n = 50
+    tl = g.integers(2, 9, n)
+    ml = g.integers(0, 3, n)
+    tok_off = np.concatenate([[0], np.cumsum(tl)]).astype(np.int64)
+    pos_off = np.concatenate([[0], np.cumsum(ml)]).astype(np.int64)
+    tokens = g.integers(0, 65536, tok_off[-1]).astype(np.uint16)  # ids above 32767 too
+    labels = g.integers(0, 65536, pos_off[-1]).astype(np.uint16)
+    pos = g.integers(0, 128, pos_off[-1]).astype(np.uint16)
+    len_a = g.integers(1, 3, n).astype(np.int32)
+    rn = g.integers(0, 2, n).astype(np.uint8)
+    t = torch.from_numpy
+    pb = PairBatch(t(tokens.view(np.int16)), t(tok_off), t(len_a), t(rn), t(pos.view(np.int16)),
+                   t(labels.view(np.int16)), t(pos_off), 11, 5, t(np.asarray([0, 20, n])), 0.0,
+                   int(pos_off[-1]))
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), [pb], seed=3, rank=0, world=1, n_sample=16)
+    got = {f[:-4]: np.load(tmp_path / 'a' / f) for f in sorted(os.listdir(tmp_path / 'a'))}
+    for k, v in got.items():
+        assert v.dtype in (np.float32, np.float64), k
+        assert np.array_equal(v, np.load(tmp_path / 'b' / (k + '.npy'))), k
+    assert got['counts'].tolist() == [n, tok_off[-1], pos_off[-1], 11, 5]
+    assert got['sums'].tolist() == [tokens.sum(dtype=np.int64), len_a.sum(), rn.sum(),
+                                    pos.sum(dtype=np.int64), labels.sum(dtype=np.int64)]
+    assert got['part_off'].tolist() == [0, 20, n]
+    q = got['sample_pair'].astype(np.int64)
+    assert len(q) == 16 and (np.diff(q) > 0).all() and q[-1] < n
+    assert np.array_equal(got['sample_tok_off'], tok_off[q])
+    assert np.array_equal(got['sample_pos_off'], pos_off[q])
+    assert np.array_equal(got['sample_num_tokens'], tl[q] + 3)
+    assert np.array_equal(got['sample_num_masked'], ml[q])
+    assert np.array_equal(got['sample_len_a'], len_a[q])
+    assert np.array_equal(got['sample_is_random_next'], rn[q])
+    rows = lambda a, off: np.concatenate([a[off[i]:off[i + 1]] for i in q])  # noqa: E731
+    assert np.array_equal(got['sample_tokens'], rows(tokens, tok_off))
+    assert np.array_equal(got['sample_pos'], rows(pos, pos_off))
+    assert np.array_equal(got['sample_labels'], rows(labels, pos_off))
+
+
+def test_plain_run_options():
+    """--steps 0 and --dump-outputs of a workload without a dump are refused before any work."""
+    for argv in (['--steps', '0'], ['--workload', 'c3', '--dump-outputs', 'x']):
+        r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')] + argv,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert r.returncode == 2 and 'bench.py: error' in r.stderr, r.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` prints the headline line without the lines
+    that --full adds, times exactly K steps, and --dump-outputs writes the last step's sample,
+    consistent with the line's own counts."""
+    import json
+    import numpy as np
+    env = dict(os.environ)
+    env.pop('WORLD_SIZE', None)
+    env.pop('LDDL_BENCH_SHARE_DEVICE', None)
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3',
+                        '--warmup', '1', '--batch-bytes', '20000000', '--dump-outputs',
+                        str(tmp_path)], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([x for x in r.stdout.splitlines() if x.startswith('{')][-1])
+    assert line['steps'] == 3 and len(line['stages_ms']['per_step_pairs']) == 3
+    assert line['ms_per_step'] > 0 and line['unit'] == 'output tokens/s'
+    for k in ('cpu_baseline', 'alt_rng', 'with_segmentation', 'pcie_inclusive', 'ref_partitioning'):
+        assert k not in line, k
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    n_pairs, n_tok = int(got['counts'][0]), int(got['counts'][1])
+    assert n_pairs == line['config']['pairs']
+    # value = output tokens ([CLS] / [SEP] included) of the K steps over their time
+    assert abs(line['value'] * line['ms_per_step'] * 1e-3 - (n_tok + 3 * n_pairs)) < 1e-6 * n_tok
+    assert got['part_off'][-1] == n_pairs and len(got['part_off']) == line['config']['partitions'] + 1
+    assert got['sample_num_tokens'].sum() == len(got['sample_tokens']) + 3 * len(got['sample_pair'])
+    assert got['sample_num_masked'].sum() == len(got['sample_pos']) == len(got['sample_labels'])
+    assert got['sample_tokens'].max() < 30522 and (got['sample_num_tokens'] <= 128).all()
+
+
 @pytest.mark.gpu
 def test_bench_c4_exchange_subline_two_ranks():
     """`bench.py --gpus 2` in the one-GPU rehearsal (LDDL_BENCH_SHARE_DEVICE=1: two ranks on
@@ -85,7 +172,7 @@ def test_bench_c4_exchange_subline_two_ranks():
     env.pop('WORLD_SIZE', None)
     r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '2', '--steps', '1',
                         '--warmup', '0', '--batch-bytes', '60000000', '--exchange-bytes', '40000000',
-                        '--no-alt-rng', '--no-segmented-line', '--no-extra-lines'],
+                        '--full', '--no-alt-rng', '--no-segmented-line', '--no-extra-lines'],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith('{')][-1])

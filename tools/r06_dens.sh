@@ -7,7 +7,7 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 120 --timeout-method threa
 tail -1 $O/tests.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_native -o run -- python -u bench.py --no-cpu-baseline --steps 3 --warmup 1 --rng native --no-alt-rng --no-segmented-line --no-extra-lines > $O/bench_native.log 2>&1 || { echo NATIVE_FAILED; exit 4; }
 python tools/prof_summary.py $O/prof_native $O/kernels_native && head -12 $O/kernels_native.txt
-timeout -k 10 300 python -u bench.py --no-cpu-baseline --steps 5 --warmup 1 --no-segmented-line --no-extra-lines > $O/bench_c2.log 2>&1 || { echo BENCH_FAILED; exit 5; }
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --steps 5 --warmup 1 --no-segmented-line --no-extra-lines > $O/bench_c2.log 2>&1 || { echo BENCH_FAILED; exit 5; }
 python - $O/bench_c2.log <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -5,9 +5,9 @@ O=gpurun_out/${1:-r06z2}
 mkdir -p $O
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('SMOKE_OK')" > $O/smoke.log 2>&1 || { echo SMOKE_FAILED; tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 500 python -u bench.py > $O/bench_c2.log 2>&1 || { echo BENCH_FAILED; tail -20 $O/bench_c2.log; exit 2; }
-timeout -k 10 500 python -u bench.py --workload c3 --no-cpu-baseline > $O/bench_c3.log 2>&1 || { echo C3_FAILED; tail -20 $O/bench_c3.log; exit 3; }
-[ -n "$WITH_C4" ] && { timeout -k 10 600 python -u bench.py --workload c4 --no-cpu-baseline --no-alt-rng > $O/bench_c4.log 2>&1 || { echo C4_FAILED; tail -20 $O/bench_c4.log; exit 4; }; }
+timeout -k 10 500 python -u bench.py --full > $O/bench_c2.log 2>&1 || { echo BENCH_FAILED; tail -20 $O/bench_c2.log; exit 2; }
+timeout -k 10 500 python -u bench.py --full --workload c3 --no-cpu-baseline > $O/bench_c3.log 2>&1 || { echo C3_FAILED; tail -20 $O/bench_c3.log; exit 3; }
+[ -n "$WITH_C4" ] && { timeout -k 10 600 python -u bench.py --full --workload c4 --no-cpu-baseline --no-alt-rng > $O/bench_c4.log 2>&1 || { echo C4_FAILED; tail -20 $O/bench_c4.log; exit 4; }; }
 python - $O <<'PY'
 import json, sys, os
 for n in [x for x in ('bench_c2', 'bench_c3', 'bench_c4') if os.path.exists(os.path.join(sys.argv[1], x + '.log'))]:

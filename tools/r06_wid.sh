@@ -10,7 +10,7 @@ i=0
 for v in base pold base pold; do
   i=$((i+1))
   lib=lddl_amd/_lib/liblddl_amd.so; [ $v != base ] && lib=lddl_amd/_lib_$v/liblddl_amd.so
-  LDDL_AMD_LIB=$lib timeout -k 10 400 python -u bench.py --no-cpu-baseline --steps 3 --warmup 1 --no-extra-lines > $O/bench_${v}_$i.log 2>&1 || { echo BENCH_FAILED $v; tail -3 $O/bench_${v}_$i.log; exit 3; }
+  LDDL_AMD_LIB=$lib timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --no-extra-lines > $O/bench_${v}_$i.log 2>&1 || { echo BENCH_FAILED $v; tail -3 $O/bench_${v}_$i.log; exit 3; }
   python - $O/bench_${v}_$i.log $v <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])

@@ -5,5 +5,5 @@ cd /root/repo
 export TMPDIR=/tmp
 O=gpurun_out/$1
 mkdir -p $O
-LDDL_BENCH_SHARE_DEVICE=1 timeout -k 10 600 python3 bench.py --gpus 2 --steps 2 --warmup 1 > $O/bench_n2.log 2>&1 || exit 1
+LDDL_BENCH_SHARE_DEVICE=1 timeout -k 10 600 python3 bench.py --full --gpus 2 --steps 2 --warmup 1 > $O/bench_n2.log 2>&1 || exit 1
 echo ALLDONE
