@@ -21,6 +21,7 @@
 //           applying the mask decisions and emitting positions + labels.
 #include <algorithm>
 #include <cstdio>
+#include <memory>
 #include <vector>
 
 #include <cstdlib>
@@ -2254,11 +2255,12 @@ using namespace lddl;
 
 // Device-resident plan of one batch of partitions (library-owned temporaries).
 struct lddl_pairs {
-  int device = 0;
   int32_t masking = 0, max_pred = 0, seq = 0, cls_id = -1, sep_id = -1;
   int64_t n_part = 0, n_pairs = 0, n_tokens = 0, n_masked = 0, n_kept_sent = 0, n_kept_doc = 0;
-  DevArena* arena = nullptr;  // the context's block cache (the context outlives its plans)
-  std::vector<DevArena::Block> allocs;
+  // every device block of the plan, from the context's arena (the context outlives its plans);
+  // lddl_pairs_destroy gives them back on its stream, a plan dropped while planning on the
+  // planning stream
+  ArenaScope mem;
   // views
   int64_t *ks_start = nullptr, *kd_off = nullptr, *kp_off = nullptr, *kscan = nullptr;
   int32_t* ks_len = nullptr;
@@ -2272,42 +2274,88 @@ struct lddl_pairs {
   int64_t* part_base = nullptr;  // [n_part + 1] first output pair of each partition
   hipEvent_t ev[2] = {nullptr, nullptr};  // around the last plan_replay_kernel launch
 
-  template <typename T>
-  int alloc(T** p, int64_t n, hipStream_t st) {
-    DevArena::Block b;
-    LDDL_HIP(arena->take(sizeof(T) * (size_t)(n > 0 ? n : 1), st, b));
-    *p = static_cast<T*>(b.p);
-    allocs.push_back(b);
-    return 0;
-  }
-  void free_one(void* p, hipStream_t st) {  // return one block early (re-plan)
-    for (size_t i = 0; i < allocs.size(); ++i)
-      if (allocs[i].p == p) {
-        arena->give(allocs[i], st);
-        allocs.erase(allocs.begin() + (ptrdiff_t)i);
-        return;
-      }
-  }
-  void release(hipStream_t st) {
-    for (DevArena::Block& b : allocs) arena->give(b, st);
-    allocs.clear();
-    for (hipEvent_t& e : ev)
-      if (e) {
-        (void)hipEventDestroy(e);
-        e = nullptr;
-      }
+  lddl_pairs(DevArena* arena, hipStream_t st) : mem(arena, st) {}
+  ~lddl_pairs() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
   }
 };
 
-#define TRY(x)                     \
-  do {                             \
-    int rc_ = (x);                 \
-    if (rc_) {                     \
-      P->release(st);              \
-      delete P;                    \
-      return rc_;                  \
-    }                              \
-  } while (0)
+// A/B knobs of the mask replay, LDDL_FY_MODE / LW / RA / PF (what they select: resolve_masks)
+struct FyKnobs {
+  int mode, lw, ra, pf;
+};
+
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// the A/B knobs take only the values a test runs (unsupported values and
+// combinations were ignored without notice)
+static int read_fy_knobs(FyKnobs* k) {
+  *k = FyKnobs{env_int("LDDL_FY_MODE", -1), env_int("LDDL_FY_LW", 16), env_int("LDDL_FY_RA", 1),
+               env_int("LDDL_FY_PF", 4)};
+  if (k->mode < -1 || k->mode > 1) LDDL_FAIL(-1, "LDDL_FY_MODE must be -1 (auto), 0 or 1");
+  if (k->lw != 16 && k->lw != 32) LDDL_FAIL(-1, "LDDL_FY_LW must be 16 or 32");
+  if (k->ra < 0 || k->ra > 3) LDDL_FAIL(-1, "LDDL_FY_RA must be 0 .. 3");
+  if (k->pf != 2 && k->pf != 4 && k->pf != 8) LDDL_FAIL(-1, "LDDL_FY_PF must be 2, 4 or 8");
+  if (k->pf != 4 && k->ra != 1) LDDL_FAIL(-1, "LDDL_FY_PF applies with LDDL_FY_RA=1 only");
+  if ((k->ra != 1 || k->pf != 4) && (k->mode == 0 || k->lw == 32))
+    LDDL_FAIL(-1, "LDDL_FY_RA / PF select 16-lane branch-free variants (not with LDDL_FY_MODE=0 "
+                  "or LDDL_FY_LW=32)");
+  return 0;
+}
+
+static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKnobs* fy) {
+  if (!c || !prm) LDDL_FAIL(-1, "null argument");
+  if (prm->seq < 5 || prm->seq > 65535) LDDL_FAIL(-1, "target_seq_length %d out of range", prm->seq);
+  if (prm->dup < 1) LDDL_FAIL(-1, "duplicate_factor must be >= 1");
+  if (prm->rng != LDDL_RNG_REPLAY && prm->rng != LDDL_RNG_NATIVE)
+    LDDL_FAIL(-1, "unknown rng mode %d", prm->rng);
+  if (prm->masking && prm->seq > kMaxSeqGather)
+    LDDL_FAIL(-1, "static masking supports target_seq_length <= %d", kMaxSeqGather);
+  if (prm->masking && (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0 ||
+                       c->tab.special_id[kMask] < 0))
+    LDDL_FAIL(-1, "static masking needs [CLS] [SEP] [MASK] in the vocab");
+  return read_fy_knobs(fy);
+}
+
+// What one planning stage hands to the next: the inputs of the call, host values read back, and
+// device temporaries that no later call on the plan reads. The temporaries come from `tmp`,
+// today the plan's own scope (they live until lddl_pairs_destroy); a scope local to
+// lddl_pairs_plan would return them when planning ends.
+struct PlanWork {
+  lddl_ctx* c;
+  const lddl_pair_params* prm;
+  const int32_t* d_ids;
+  const int64_t* d_part_seed;
+  int64_t n_sent, n_part;
+  hipStream_t st;
+  ArenaScope& tmp;
+  FyKnobs fy;
+  // compact_inputs
+  int64_t* scratch = nullptr;  // scan scratch of the compaction and of the re-plan loop
+  int64_t n_kept_tok = 0;
+  unsigned long long max_docs = 0;  // kept documents of the largest partition
+  // plan_replay
+  int32_t* jseq = nullptr;
+  int64_t* part_npairs = nullptr;
+  SlotPool* spool = nullptr;
+  void* jpool = nullptr;
+  int64_t max_np = 1;  // pairs of the largest partition
+  // shuffle_partitions
+  PairMaps M{nullptr, nullptr, nullptr, nullptr};
+  // layout
+  int2* pcnt = nullptr;
+  int64_t* scr2 = nullptr;
+#ifdef LDDL_STAMPS
+  uint64_t *d_stamps = nullptr, *d_tl = nullptr;
+#endif
+};
+
+// replay mode: the planner launch's tail workgroups pack `dense` (plan_replay_kernel)
+static bool dense_in_plan(const PlanWork& W) { return W.prm->rng == LDDL_RNG_REPLAY && W.n_part > 0; }
 
 // ceil(p * 2^53): random() < p  <=>  N < this (N = 53-bit integer behind random())
 static uint64_t short_threshold(double p) {
@@ -2321,21 +2369,125 @@ struct I32 {
   __device__ int64_t operator()(int64_t i) const { return v[i]; }
 };
 
-// LDDL_RNG_NATIVE control plane: count pass, unit scan, emit pass, mask offsets + masks, order.
-static int plan_native(lddl_pairs* P, lddl_ctx* c, const lddl_pair_params* prm,
-                       const int64_t* d_part_seed, int64_t n_part, hipStream_t st) {
-  NativeArgs A{};
+// Drop empty sentences and documents: the kept-sentence tables, the partitions' kept-document
+// offsets and the dense token buffer.
+static int compact_inputs(lddl_pairs* P, PlanWork& W, const int64_t* d_sent_off,
+                          const int32_t* d_sent_len, const int64_t* d_doc_sent_off, int64_t n_doc,
+                          const int64_t* d_part_doc_off) {
+  const int64_t n_sent = W.n_sent, n_part = W.n_part;
+  hipStream_t st = W.st;
+  int rc;
+  int64_t *ks_pos, *tok_pos, *kd_pos;
+  const int64_t nscr = 2 * scan_scratch_elems(std::max(n_sent, n_doc) + n_part + 1);  // (dual scans)
+  // kept-sentence index and token offset of every sentence in one scan
+  if ((rc = W.tmp.take(&W.scratch, nscr)) || (rc = W.tmp.take(&ks_pos, n_sent + 1)) ||
+      (rc = W.tmp.take(&tok_pos, n_sent + 1)))
+    return rc;
+  LDDL_HIP(scan_exclusive2(SentCounts{d_sent_len}, n_sent, ks_pos, tok_pos, W.scratch, st));
+  if ((rc = W.tmp.take(&kd_pos, n_doc + 1))) return rc;
+  LDDL_HIP(scan_exclusive(KeepDoc{ks_pos, d_doc_sent_off}, n_doc, kd_pos, W.scratch, st));
+  int64_t h_counts[3];
+  LDDL_HIP(hipMemcpyAsync(&h_counts[0], ks_pos + n_sent, 8, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipMemcpyAsync(&h_counts[1], kd_pos + n_doc, 8, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipMemcpyAsync(&h_counts[2], tok_pos + n_sent, 8, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipStreamSynchronize(st));
+  P->n_kept_sent = h_counts[0];
+  P->n_kept_doc = h_counts[1];
+  W.n_kept_tok = h_counts[2];  // (dropped sentences have no tokens)
+  unsigned long long* d_max_docs;
+  if ((rc = P->mem.take(&P->ks_start, P->n_kept_sent)) || (rc = P->mem.take(&P->ks_len, P->n_kept_sent)) ||
+      (rc = P->mem.take(&P->kscan, P->n_kept_sent + 1)) || (rc = P->mem.take(&P->kd_off, P->n_kept_doc + 1)) ||
+      (rc = P->mem.take(&P->kp_off, n_part + 1)) || (rc = W.tmp.take(&d_max_docs, 1)))
+    return rc;
+  hipLaunchKernelGGL(scatter_sentences_kernel, dim3((unsigned)((n_sent + 256) / 256)), dim3(256), 0,
+                     st, d_sent_off, d_sent_len, n_sent, ks_pos, tok_pos, P->ks_start, P->ks_len,
+                     P->kscan);
+  hipLaunchKernelGGL(scatter_docs_kernel, dim3((unsigned)((n_doc + 256) / 256)), dim3(256), 0, st,
+                     d_doc_sent_off, n_doc, ks_pos, kd_pos, P->kd_off);
+  LDDL_HIP(hipMemsetAsync(d_max_docs, 0, 8, st));
+  hipLaunchKernelGGL(part_offsets_kernel, dim3((unsigned)((n_part + 256) / 256)), dim3(256), 0, st,
+                     d_part_doc_off, n_part, kd_pos, P->kp_off, d_max_docs);
+  LDDL_HIP(hipGetLastError());
+  LDDL_HIP(hipMemcpyAsync(&W.max_docs, d_max_docs, 8, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipStreamSynchronize(st));
+  // dense kept tokens, 8 tokens of padding on both sides: the gather's 4- and 8-token loads may
+  // overhang a window
+  const int32_t ib = W.c->id_bytes();
+  uint8_t* raw;
+  if ((rc = P->mem.take(&raw, (W.n_kept_tok + 16) * ib))) return rc;
+  P->dense = IdPtr{raw + 8 * ib, ib};
+  if (P->n_kept_sent && !dense_in_plan(W))
+    hipLaunchKernelGGL(densify_kernel, dim3((unsigned)((P->n_kept_sent + 255) / 256)), dim3(256), 0,
+                       st, P->ks_start, P->ks_len, P->kscan, P->n_kept_sent, W.d_ids, P->dense);
+  LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
+// The gather records + output-order scans (tok_off, pos_off) of the plan's pairs.
+static int layout_alloc(lddl_pairs* P, PlanWork& W) {
+  const int64_t npairs = P->n_pairs;
+  int rc;
+  if ((rc = P->mem.take(&P->tok_off, npairs + 1)) || (rc = P->mem.take(&P->rec, npairs)) ||
+      (rc = W.tmp.take(&W.pcnt, npairs)) || (rc = W.tmp.take(&W.scr2, 2 * scan_scratch_elems(npairs))))
+    return rc;
+  if (P->masking && (rc = P->mem.take(&P->pos_off, npairs + 1))) return rc;
+  return 0;
+}
+
+static int layout_scan(lddl_pairs* P, PlanWork& W) {  // tok_off (and pos_off) from the counts
+  if (P->masking)
+    LDDL_HIP(scan_exclusive2(PairCounts{W.pcnt}, P->n_pairs, P->tok_off, P->pos_off, W.scr2, W.st));
+  else
+    LDDL_HIP(scan_exclusive(PairTokens{W.pcnt}, P->n_pairs, P->tok_off, W.scr2, W.st));
+  return 0;
+}
+
+// gather records from the output order (src): the native path, and replay without masking
+static int layout_pairs(lddl_pairs* P, PlanWork& W) {
+  int rc;
+  if ((rc = layout_alloc(P, W))) return rc;
+  const int64_t npairs = P->n_pairs;
+  if (npairs)
+    hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, W.st,
+                       P->src, npairs, P->desc, P->kscan, P->masking ? P->nmask : nullptr,
+                       P->moff, P->rec, W.pcnt);
+  LDDL_HIP(hipGetLastError());
+  return layout_scan(P, W);
+}
+
+// the kept corpus and the call's parameters, as both planners' kernels take them
+template <typename Args>
+static void fill_plan_args(Args& A, const lddl_pairs* P, const PlanWork& W) {
+  A.kscan = P->kscan;
   A.ks_len = P->ks_len;
   A.kd_off = P->kd_off;
   A.kp_off = P->kp_off;
-  A.kscan = P->kscan;
   A.dense = P->dense;
-  A.part_seed = d_part_seed;
-  A.n_part = n_part;
+  A.part_seed = W.d_part_seed;
+  A.n_part = (decltype(A.n_part))W.n_part;
+  A.seq = W.prm->seq;
+  A.dup = W.prm->dup;
+  A.masking = W.prm->masking;
+  A.vocab_size = W.c->vocab_size;
+  A.cls_id = P->cls_id;
+  A.sep_id = P->sep_id;
+  A.mask_id = W.c->tab.special_id[kMask];
+  A.ratio = W.prm->masked_lm_ratio;
+  A.k_short = short_threshold(W.prm->short_seq_prob);
+}
+
+// LDDL_RNG_NATIVE control plane: count pass, unit scan, emit pass, mask offsets + masks, order,
+// layout.
+static int plan_native(lddl_pairs* P, PlanWork& W) {
+  const lddl_pair_params* prm = W.prm;
+  const int64_t n_part = W.n_part;
+  hipStream_t st = W.st;
+  NativeArgs A{};
+  fill_plan_args(A, P, W);
   int64_t kp_ends[2] = {0, 0};  // kept documents covered by the partitions
   unsigned long long need_max = 0, *d_need;
   int rc;
-  if ((rc = P->alloc(&d_need, 1, st))) return rc;
+  if ((rc = W.tmp.take(&d_need, 1))) return rc;
   LDDL_HIP(hipMemsetAsync(d_need, 0, 8, st));
   if (n_part)
     hipLaunchKernelGGL(native_part_need_kernel, dim3((unsigned)((n_part + 255) / 256)), dim3(256), 0, st,
@@ -2347,15 +2499,6 @@ static int plan_native(lddl_pairs* P, lddl_ctx* c, const lddl_pair_params* prm,
   A.unit0 = (int64_t)prm->dup * kp_ends[0];
   A.n_units = (int64_t)prm->dup * (kp_ends[1] - kp_ends[0]);
   A.native_seed = prm->native_seed;
-  A.k_short = short_threshold(prm->short_seq_prob);
-  A.seq = prm->seq;
-  A.dup = prm->dup;
-  A.masking = prm->masking;
-  A.cls_id = c->tab.special_id[kCls];
-  A.sep_id = c->tab.special_id[kSep];
-  A.mask_id = c->tab.special_id[kMask];
-  A.vocab_size = c->vocab_size;
-  A.ratio = prm->masked_lm_ratio;
   const int64_t nu = A.n_units;
   // walk tables in LDS up to 96 KB per workgroup; larger partitions read a global prefix
   int64_t kLdsWordsCap = 24576;
@@ -2363,11 +2506,11 @@ static int plan_native(lddl_pairs* P, lddl_ctx* c, const lddl_pair_params* prm,
   const int32_t lds_words = (int32_t)std::max<int64_t>(
       1, std::min<int64_t>((int64_t)need_max, kLdsWordsCap));
   int64_t *uoff, *scr, *g_pre = nullptr;
-  if ((rc = P->alloc(&A.ucnt, nu, st)) || (rc = P->alloc(&uoff, nu + 1, st)) ||
-      (rc = P->alloc(&scr, scan_scratch_elems(std::max(nu, P->n_kept_sent) + 1), st)))
+  if ((rc = W.tmp.take(&A.ucnt, nu)) || (rc = W.tmp.take(&uoff, nu + 1)) ||
+      (rc = W.tmp.take(&scr, scan_scratch_elems(std::max(nu, P->n_kept_sent) + 1))))
     return rc;
   if ((int64_t)need_max > kLdsWordsCap) {
-    if ((rc = P->alloc(&g_pre, P->n_kept_sent + 1, st))) return rc;
+    if ((rc = W.tmp.take(&g_pre, P->n_kept_sent + 1))) return rc;
     LDDL_HIP(scan_exclusive(KeptLenOnly{P->ks_len}, P->n_kept_sent, g_pre, scr, st));
   }
   LDDL_HIP(hipEventRecord(P->ev[0], st));
@@ -2382,12 +2525,12 @@ static int plan_native(lddl_pairs* P, lddl_ctx* c, const lddl_pair_params* prm,
   const int64_t n = P->n_pairs;
   A.uoff = uoff;
   A.n_pairs = n;
-  if ((rc = P->alloc(&P->part_base, n_part + 1, st)) || (rc = P->alloc(&P->desc, n, st)) ||
-      (rc = P->alloc(&A.ppart, n, st)) || (rc = P->alloc(&P->src, n, st)))
+  if ((rc = P->mem.take(&P->part_base, n_part + 1)) || (rc = P->mem.take(&P->desc, n)) ||
+      (rc = W.tmp.take(&A.ppart, n)) || (rc = P->mem.take(&P->src, n)))
     return rc;
   if (prm->masking &&
-      ((rc = P->alloc(&P->nmask, n, st)) || (rc = P->alloc(&A.ncand, n, st)) ||
-       (rc = P->alloc(&P->moff, n + 1, st)) || (rc = P->alloc(&scr, scan_scratch_elems(n + 1), st))))
+      ((rc = P->mem.take(&P->nmask, n)) || (rc = W.tmp.take(&A.ncand, n)) ||
+       (rc = P->mem.take(&P->moff, n + 1)) || (rc = W.tmp.take(&scr, scan_scratch_elems(n + 1)))))
     return rc;
   hipLaunchKernelGGL(native_part_base_kernel, dim3((unsigned)((n_part + 256) / 256)), dim3(256), 0,
                      st, P->kp_off, n_part, prm->dup, uoff, P->part_base);
@@ -2403,7 +2546,7 @@ static int plan_native(lddl_pairs* P, lddl_ctx* c, const lddl_pair_params* prm,
     LDDL_HIP(scan_exclusive(I32{P->nmask}, n, P->moff, scr, st));
     LDDL_HIP(hipMemcpyAsync(&P->n_masked, P->moff + n, 8, hipMemcpyDeviceToHost, st));
     LDDL_HIP(hipStreamSynchronize(st));
-    if ((rc = P->alloc(&P->mpos, P->n_masked, st)) || (rc = P->alloc(&P->mtok, P->n_masked, st)))
+    if ((rc = P->mem.take(&P->mpos, P->n_masked)) || (rc = P->mem.take(&P->mtok, P->n_masked)))
       return rc;
     A.moff = P->moff;
     A.mpos = P->mpos;
@@ -2423,206 +2566,68 @@ static int plan_native(lddl_pairs* P, lddl_ctx* c, const lddl_pair_params* prm,
   if (n) hipLaunchKernelGGL(order_native_kernel, dim3(gp), dim3(256), 0, st, A);
   LDDL_HIP(hipGetLastError());
   LDDL_HIP(hipEventRecord(P->ev[1], st));
-  return 0;
+  return layout_pairs(P, W);
 }
 
-extern "C" int lddl_pairs_plan(lddl_ctx* c, void* stream, const lddl_pair_params* prm,
-                               const int64_t* d_sent_off, const int32_t* d_ids,
-                               const int32_t* d_sent_len, int64_t n_sent,
-                               const int64_t* d_doc_sent_off, int64_t n_doc,
-                               const int64_t* d_part_doc_off, const int64_t* d_part_seed,
-                               int64_t n_part, lddl_pairs** out, int64_t* counts) {
-  *out = nullptr;
-  if (!c || !prm) LDDL_FAIL(-1, "null argument");
-  if (prm->seq < 5 || prm->seq > 65535) LDDL_FAIL(-1, "target_seq_length %d out of range", prm->seq);
-  if (prm->dup < 1) LDDL_FAIL(-1, "duplicate_factor must be >= 1");
-  if (prm->rng != LDDL_RNG_REPLAY && prm->rng != LDDL_RNG_NATIVE)
-    LDDL_FAIL(-1, "unknown rng mode %d", prm->rng);
-  const int32_t cls = c->tab.special_id[kCls], sep = c->tab.special_id[kSep],
-                msk = c->tab.special_id[kMask];
-  if (prm->masking && prm->seq > kMaxSeqGather)
-    LDDL_FAIL(-1, "static masking supports target_seq_length <= %d", kMaxSeqGather);
-  if (prm->masking && (cls < 0 || sep < 0 || msk < 0))
-    LDDL_FAIL(-1, "static masking needs [CLS] [SEP] [MASK] in the vocab");
-  hipStream_t st = as_stream(stream);
-  auto* P = new lddl_pairs();
-  P->device = c->device;
-  P->arena = &c->arena;
-  P->n_part = n_part;
-  P->masking = prm->masking;
-  P->seq = prm->seq;
-  P->cls_id = cls;
-  P->sep_id = sep;
-  TRY(hipEventCreate(&P->ev[0]) == hipSuccess && hipEventCreate(&P->ev[1]) == hipSuccess
-          ? 0 : (set_error("hipEventCreate failed"), -100));
-  int64_t *ks_pos, *tok_pos, *kd_pos, *scratch, *part_npairs, *part_base;
-  const int64_t nscr = 2 * scan_scratch_elems(std::max(n_sent, n_doc) + n_part + 1);  // (dual scans)
-  TRY(P->alloc(&scratch, nscr, st));
-  // compaction: kept-sentence index and token offset of every sentence in one scan
-  TRY(P->alloc(&ks_pos, n_sent + 1, st));
-  TRY(P->alloc(&tok_pos, n_sent + 1, st));
-  if (scan_exclusive2(SentCounts{d_sent_len}, n_sent, ks_pos, tok_pos, scratch, st) != hipSuccess)
-    TRY(-100);
-  TRY(P->alloc(&kd_pos, n_doc + 1, st));
-  if (scan_exclusive(KeepDoc{ks_pos, d_doc_sent_off}, n_doc, kd_pos, scratch, st) != hipSuccess)
-    TRY(-100);
-  int64_t h_counts[3];
-  LDDL_HIP(hipMemcpyAsync(&h_counts[0], ks_pos + n_sent, 8, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipMemcpyAsync(&h_counts[1], kd_pos + n_doc, 8, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipMemcpyAsync(&h_counts[2], tok_pos + n_sent, 8, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipStreamSynchronize(st));
-  P->n_kept_sent = h_counts[0];
-  P->n_kept_doc = h_counts[1];
-  const int64_t n_kept_tok = h_counts[2];  // (dropped sentences have no tokens)
-  TRY(P->alloc(&P->ks_start, P->n_kept_sent, st));
-  TRY(P->alloc(&P->ks_len, P->n_kept_sent, st));
-  TRY(P->alloc(&P->kscan, P->n_kept_sent + 1, st));
-  TRY(P->alloc(&P->kd_off, P->n_kept_doc + 1, st));
-  TRY(P->alloc(&P->kp_off, n_part + 1, st));
-  hipLaunchKernelGGL(scatter_sentences_kernel, dim3((unsigned)((n_sent + 256) / 256)), dim3(256), 0,
-                     st, d_sent_off, d_sent_len, n_sent, ks_pos, tok_pos, P->ks_start, P->ks_len,
-                     P->kscan);
-  hipLaunchKernelGGL(scatter_docs_kernel, dim3((unsigned)((n_doc + 256) / 256)), dim3(256), 0, st,
-                     d_doc_sent_off, n_doc, ks_pos, kd_pos, P->kd_off);
-  unsigned long long* d_max_docs;
-  TRY(P->alloc(&d_max_docs, 1, st));
-  LDDL_HIP(hipMemsetAsync(d_max_docs, 0, 8, st));
-  hipLaunchKernelGGL(part_offsets_kernel, dim3((unsigned)((n_part + 256) / 256)), dim3(256), 0, st,
-                     d_part_doc_off, n_part, kd_pos, P->kp_off, d_max_docs);
-  LDDL_HIP(hipGetLastError());
-  // dense kept tokens
-  unsigned long long max_docs = 0;
-  LDDL_HIP(hipMemcpyAsync(&max_docs, d_max_docs, 8, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipStreamSynchronize(st));
-  // 8 tokens of padding on both sides: the gather's 4- and 8-token loads may overhang a window
-  {
-    const int32_t ib = c->id_bytes();
-    uint8_t* raw;
-    TRY(P->alloc(&raw, (n_kept_tok + 16) * ib, st));
-    P->dense = IdPtr{raw + 8 * ib, ib};
-  }
-  // replay mode: the planner launch's tail workgroups pack `dense` (plan_replay_kernel)
-  const bool dense_in_plan = prm->rng == LDDL_RNG_REPLAY && n_part > 0;
-  if (P->n_kept_sent && !dense_in_plan)
-    hipLaunchKernelGGL(densify_kernel, dim3((unsigned)((P->n_kept_sent + 255) / 256)), dim3(256), 0,
-                       st, P->ks_start, P->ks_len, P->kscan, P->n_kept_sent, d_ids, P->dense);
-  LDDL_HIP(hipGetLastError());
-  // plan
+// LDDL_RNG_REPLAY planner: sizes the mask pools, launches plan_replay_kernel (between the plan's
+// two events) and, when a pool overflowed, once more with the exact sizes.
+static int plan_replay(lddl_pairs* P, PlanWork& W) {
+  const lddl_pair_params* prm = W.prm;
+  const int64_t n_part = W.n_part;
+  hipStream_t st = W.st;
+  if (prm->seq > 512) LDDL_FAIL(-1, "replay planner supports target_seq_length <= 512");
   const int64_t slots = (int64_t)prm->dup * P->n_kept_sent;
-  int32_t max_pred = 0;
-  if (prm->masking) {
-    max_pred = (int32_t)rint((double)prm->seq * prm->masked_lm_ratio);
-    if (max_pred < 1) max_pred = 1;
-    if (max_pred > prm->seq) max_pred = prm->seq;
-
-  }
-  P->max_pred = max_pred;
-  // the gather records + output-order scans (tok_off, pos_off) of the plan's pairs
-  int2* pcnt = nullptr;
-  int64_t* scr2 = nullptr;
-  auto alloc_layout = [&](int64_t npairs) -> int {
-    int rc;
-    if ((rc = P->alloc(&P->tok_off, npairs + 1, st)) || (rc = P->alloc(&P->rec, npairs, st)) ||
-        (rc = P->alloc(&pcnt, npairs, st)) || (rc = P->alloc(&scr2, 2 * scan_scratch_elems(npairs), st)))
-      return rc;
-    if (prm->masking && (rc = P->alloc(&P->pos_off, npairs + 1, st))) return rc;
-    return 0;
-  };
-  auto scan_only = [&](hipStream_t s) -> int {  // tok_off (and pos_off) from the counts
-    if (prm->masking)
-      LDDL_HIP(scan_exclusive2(PairCounts{pcnt}, P->n_pairs, P->tok_off, P->pos_off, scr2, s));
-    else
-      LDDL_HIP(scan_exclusive(PairTokens{pcnt}, P->n_pairs, P->tok_off, scr2, s));
-    return 0;
-  };
-  // gather records from the output order (src): the native path, and replay without masking
-  auto prep_and_scan = [&](hipStream_t s) -> int {
-    const int64_t npairs = P->n_pairs;
-    if (npairs)
-      hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, s,
-                         P->src, npairs, P->desc, P->kscan, prm->masking ? P->nmask : nullptr,
-                         P->moff, P->rec, pcnt);
-    LDDL_HIP(hipGetLastError());
-    return scan_only(s);
-  };
-  if (prm->rng == LDDL_RNG_NATIVE) {
-    TRY(plan_native(P, c, prm, d_part_seed, n_part, st));
-  } else {
-  int32_t* jseq;
-  TRY(P->alloc(&P->desc, slots, st));
-  TRY(P->alloc(&P->order, slots, st));
-  TRY(P->alloc(&jseq, slots, st));
-  TRY(P->alloc(&part_npairs, n_part + 1, st));
-  SlotPool* spool = nullptr;
-  if (prm->masking) TRY(P->alloc(&spool, slots, st));
+  int rc;
+  if ((rc = P->mem.take(&P->desc, slots)) || (rc = P->mem.take(&P->order, slots)) ||
+      (rc = W.tmp.take(&W.jseq, slots)) || (rc = W.tmp.take(&W.part_npairs, n_part + 1)))
+    return rc;
+  if (prm->masking && (rc = W.tmp.take(&W.spool, slots))) return rc;
   PlanArgs A{};
-  A.kscan = P->kscan;
-  A.ks_len = P->ks_len;
-  A.kd_off = P->kd_off;
-  A.kp_off = P->kp_off;
+  fill_plan_args(A, P, W);
   A.ks_start = P->ks_start;
-  A.ids = d_ids;
-  A.dense = P->dense;
-  A.n_kept_sent = dense_in_plan ? P->n_kept_sent : 0;
-  A.n_part = (int32_t)n_part;
+  A.ids = W.d_ids;
+  A.n_kept_sent = dense_in_plan(W) ? P->n_kept_sent : 0;
   A.n_dense_wg = 4096;
-  A.part_seed = d_part_seed;
-  A.seq = prm->seq;
-  A.dup = prm->dup;
-  A.masking = prm->masking;
-  A.vocab_size = c->vocab_size;
-  A.cls_id = cls;
-  A.sep_id = sep;
-  A.mask_id = msk;
-  A.max_pred = max_pred;
+  A.max_pred = P->max_pred;
   A.short_seq_prob = prm->short_seq_prob;
-  A.ratio = prm->masked_lm_ratio;
-  A.k_short = short_threshold(prm->short_seq_prob);
   A.seq_r64 = ((prm->seq + 63) / 64) * 64;
   A.desc = P->desc;
-  A.jseq = jseq;
-  A.spool = spool;
-  A.part_npairs = part_npairs;
+  A.jseq = W.jseq;
+  A.spool = W.spool;
+  A.part_npairs = W.part_npairs;
 #ifdef LDDL_STAMPS
-  uint64_t* d_stamps;
-  TRY(P->alloc(&d_stamps, n_part * kStampRegions, st));
-  LDDL_HIP(hipMemsetAsync(d_stamps, 0, 8 * n_part * kStampRegions, st));
-  A.stamps = d_stamps;
-  uint64_t* d_tl;
-  TRY(P->alloc(&d_tl, n_part * 2, st));
-  LDDL_HIP(hipMemsetAsync(d_tl, 0, 16 * n_part, st));
-  A.tl = d_tl;
+  if ((rc = W.tmp.take(&W.d_stamps, n_part * kStampRegions)) || (rc = W.tmp.take(&W.d_tl, n_part * 2)))
+    return rc;
+  LDDL_HIP(hipMemsetAsync(W.d_stamps, 0, 8 * n_part * kStampRegions, st));
+  LDDL_HIP(hipMemsetAsync(W.d_tl, 0, 16 * n_part, st));
+  A.stamps = W.d_stamps;
+  A.tl = W.d_tl;
 #endif
-  if (prm->seq > 512) TRY((set_error("replay planner supports target_seq_length <= 512"), -1));
   const size_t lds = 4 * (kN + kLook) + 4 * (kDocLds + 4) + 16;  // ~4.8 KB: 7 waves/SIMD fit
   // pools: decisions (int32, shuffled order) and shuffle draws (uint16), sized from the kept
   // tokens (expected use ~0.15 * 1.5 and ~1.5 times dup * tokens); a plan that outgrows them
   // reports the exact sizes and is planned again (deterministic replay)
   unsigned long long* pool_ctl;  // [0] masks used, [1] overflow flag, [2] draws used, [3] max pairs
-  TRY(P->alloc(&pool_ctl, 4, st));
-  TRY(P->alloc(&part_base, n_part + 1, st));
-  P->part_base = part_base;
-  int64_t max_np = 1;
+  if ((rc = W.tmp.take(&pool_ctl, 4)) || (rc = P->mem.take(&P->part_base, n_part + 1))) return rc;
   int64_t cap = 0, jcap = 0;
-  void* jpool = nullptr;
   const int jbytes = prm->seq <= 256 ? 1 : 2;  // every draw j_i < nc <= seq - 3
-  if (prm->masking && n_sent) {
-    const int64_t kept_tokens = n_kept_tok;
-    cap = (int64_t)(2.0 * prm->masked_lm_ratio * prm->dup * (double)kept_tokens) +
+  if (prm->masking && W.n_sent) {
+    cap = (int64_t)(2.0 * prm->masked_lm_ratio * prm->dup * (double)W.n_kept_tok) +
           (int64_t)prm->dup * P->n_kept_sent / 2 + kPoolChunk * (n_part + 16);
-    jcap = (int64_t)(1.6 * prm->dup * (double)kept_tokens) + 8 * slots +
+    jcap = (int64_t)(1.6 * prm->dup * (double)W.n_kept_tok) + 8 * slots +
            kPoolChunk * (n_part + 16);  // + the 16-entry alignment of every pair's draws
     if (const char* e = getenv("LDDL_AMD_MASK_POOL")) cap = atoll(e);  // tests: force a re-plan
   }
   // SlotPool keeps pool offsets as 32-bit multiples of 8 / 16 entries
   if (cap / 8 >= (int64_t)UINT32_MAX || jcap / 16 >= (int64_t)UINT32_MAX)
-    TRY((set_error("batch too large for the mask pools (split it into smaller GPU batches)"), -1));
+    LDDL_FAIL(-1, "batch too large for the mask pools (split it into smaller GPU batches)");
   for (int attempt = 0; n_part; ++attempt) {
     int32_t* mtok = nullptr;
+    uint8_t* jpool = nullptr;
     if (prm->masking) {
       LDDL_HIP(hipMemsetAsync(pool_ctl, 0, 32, st));
-      TRY(P->alloc(&mtok, cap + 4, st));
-      TRY(P->alloc(reinterpret_cast<uint8_t**>(&jpool), jbytes * (jcap + 16), st));
+      if ((rc = P->mem.take(&mtok, cap + 4)) || (rc = W.tmp.take(&jpool, jbytes * (jcap + 16))))
+        return rc;
     }
     A.mtok = mtok;
     A.jpool = jpool;
@@ -2632,62 +2637,63 @@ extern "C" int lddl_pairs_plan(lddl_ctx* c, void* stream, const lddl_pair_params
     A.pool_used = pool_ctl;
     A.overflow = reinterpret_cast<int32_t*>(pool_ctl + 1);
     LDDL_HIP(hipEventRecord(P->ev[0], st));
-    {
-      const dim3 grid((unsigned)n_part + (A.n_kept_sent ? (unsigned)A.n_dense_wg : 0u));
-      const bool docs_lds = max_docs + 1 <= (unsigned long long)kDocLds;
-      if (docs_lds && jbytes == 1)
-        hipLaunchKernelGGL((plan_replay_kernel<true, 1>), grid, dim3(64), lds, st, A);
-      else if (docs_lds)
-        hipLaunchKernelGGL((plan_replay_kernel<true, 2>), grid, dim3(64), lds, st, A);
-      else if (jbytes == 1)
-        hipLaunchKernelGGL((plan_replay_kernel<false, 1>), grid, dim3(64), lds, st, A);
-      else
-        hipLaunchKernelGGL((plan_replay_kernel<false, 2>), grid, dim3(64), lds, st, A);
-    }
+    const dim3 grid((unsigned)n_part + (A.n_kept_sent ? (unsigned)A.n_dense_wg : 0u));
+    const bool docs_lds = W.max_docs + 1 <= (unsigned long long)kDocLds;  // document table in LDS
+    auto kern = docs_lds ? (jbytes == 1 ? plan_replay_kernel<true, 1> : plan_replay_kernel<true, 2>)
+                         : (jbytes == 1 ? plan_replay_kernel<false, 1> : plan_replay_kernel<false, 2>);
+    hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, A);
     LDDL_HIP(hipGetLastError());
     LDDL_HIP(hipEventRecord(P->ev[1], st));
     // pairs per partition -> output offsets and the largest count, read back with the pool
     // counters in the planner's one sync
     if (!prm->masking) LDDL_HIP(hipMemsetAsync(pool_ctl, 0, 32, st));
-    if (scan_exclusive(Identity{part_npairs}, n_part, part_base, scratch, st) != hipSuccess) TRY(-100);
-    hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, part_npairs, n_part, pool_ctl + 3);
+    LDDL_HIP(scan_exclusive(Identity{W.part_npairs}, n_part, P->part_base, W.scratch, st));
+    hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs, n_part, pool_ctl + 3);
     unsigned long long ctl[4];
     LDDL_HIP(hipMemcpyAsync(ctl, pool_ctl, 32, hipMemcpyDeviceToHost, st));
-    LDDL_HIP(hipMemcpyAsync(&P->n_pairs, part_base + n_part, 8, hipMemcpyDeviceToHost, st));
+    LDDL_HIP(hipMemcpyAsync(&P->n_pairs, P->part_base + n_part, 8, hipMemcpyDeviceToHost, st));
     LDDL_HIP(hipStreamSynchronize(st));
-    max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
+    W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
     if (!prm->masking) break;
     if (!ctl[1]) {
       P->mtok = mtok;
-      TRY(P->alloc(&P->mpos, (int64_t)ctl[0], st));
+      W.jpool = jpool;
+      if ((rc = P->mem.take(&P->mpos, (int64_t)ctl[0]))) return rc;
       break;
     }
-    P->free_one(mtok, st);
-    P->free_one(jpool, st);
-    jpool = nullptr;
-    if (attempt > 0) TRY((set_error("mask pool overflow after resize"), -1));
+    P->mem.give(mtok);
+    W.tmp.give(jpool);
+    if (attempt > 0) LDDL_FAIL(-1, "mask pool overflow after resize");
     cap = (int64_t)ctl[0] + 1024;
     jcap = (int64_t)ctl[2] + 1024;
   }
-  // the pair maps (see PairMaps): with masking the planner-order slots and their output
-  // positions (the mask replay writes each pair's gather record there), else the output order
-  PairMaps M{part_base, nullptr, nullptr, nullptr};
+  return 0;
+}
+
+// random.shuffle(partition_pairs), alone on the stream (its blocks need 16 waves and ~90 KB of
+// LDS per CU: beside fy_resolve's small blocks on a second stream they waited for CUs to
+// drain, 10.3 ms against ~2 alone); its last pass writes the pair maps (see PairMaps): with
+// masking the planner-order slots and their output positions (the mask replay writes each
+// pair's gather record there), else the output order
+static int shuffle_partitions(lddl_pairs* P, PlanWork& W) {
+  const lddl_pair_params* prm = W.prm;
+  const int64_t n_part = W.n_part;
+  hipStream_t st = W.st;
+  int rc;
+  PairMaps& M = W.M;
+  M.part_base = P->part_base;
   if (prm->masking) {
-    TRY(P->alloc(&M.slots, P->n_pairs, st));
-    TRY(P->alloc(&M.dstq, P->n_pairs, st));
+    if ((rc = W.tmp.take(&M.slots, P->n_pairs)) || (rc = W.tmp.take(&M.dstq, P->n_pairs))) return rc;
   } else {
-    TRY(P->alloc(&P->src, P->n_pairs, st));
+    if ((rc = P->mem.take(&P->src, P->n_pairs))) return rc;
     M.src = P->src;
   }
-  // random.shuffle(partition_pairs), alone on the stream (its blocks need 16 waves and ~90 KB of
-  // LDS per CU: beside fy_resolve's small blocks on a second stream they waited for CUs to
-  // drain, 10.3 ms against ~2 alone); its last pass writes the pair maps
   if (n_part) {
-    const int64_t cap = max_np;
+    const int64_t cap = W.max_np;
     // dynamic-LDS budget of the swap kernel: what the device grants a block (160 KiB on
     // gfx950), minus headroom for the kernel's static LDS
-    const size_t kLdsBudget = std::min<size_t>(150 * 1024, c->lds_per_block > 10 * 1024
-                                                               ? c->lds_per_block - 10 * 1024 : 0);
+    const size_t kLdsBudget = std::min<size_t>(150 * 1024, W.c->lds_per_block > 10 * 1024
+                                                               ? W.c->lds_per_block - 10 * 1024 : 0);
     const bool force_global = getenv("LDDL_SHUFFLE_GLOBAL") != nullptr;  // tests: the large-partition path
     // partitions of <= cap_lds pairs: the parallel bucket-sort resolve (three 16-bit LDS tables);
     // larger ones: one lane swapping in global memory
@@ -2695,138 +2701,174 @@ extern "C" int lddl_pairs_plan(lddl_ctx* c, void* stream, const lddl_pair_params
     if (cap_lds > 0)
       hipLaunchKernelGGL(shuffle_sort_kernel, dim3((unsigned)n_part), dim3(kShufThreads),
                          (size_t)6 * (size_t)((cap_lds + 2) & ~1), st, P->kd_off, P->kp_off,
-                         prm->dup, part_npairs, jseq, P->order, (int32_t)cap_lds, M);
+                         prm->dup, W.part_npairs, W.jseq, P->order, (int32_t)cap_lds, M);
     if (cap > cap_lds) {  // partitions beyond the LDS tables: swaps in global memory, then the maps
       hipLaunchKernelGGL(apply_shuffle_kernel, dim3((unsigned)n_part), dim3(64), 0, st, P->kd_off,
-                         P->kp_off, prm->dup, part_npairs, jseq, P->order, cap_lds);
+                         P->kp_off, prm->dup, W.part_npairs, W.jseq, P->order, cap_lds);
       hipLaunchKernelGGL(map_pairs_kernel, dim3((unsigned)n_part), dim3(256), 0, st, P->kd_off,
-                         P->kp_off, prm->dup, part_base, (const int32_t*)P->order, M.src, M.slots,
+                         P->kp_off, prm->dup, M.part_base, (const int32_t*)P->order, M.src, M.slots,
                          M.dstq);
     }
   }
   LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
 #ifdef LDDL_STAMPS
-  {
-    std::vector<uint64_t> h(n_part * kStampRegions);
-    LDDL_HIP(hipMemcpyAsync(h.data(), d_stamps, 8 * h.size(), hipMemcpyDeviceToHost, st));
-    LDDL_HIP(hipStreamSynchronize(st));
-    double tot[kStampRegions] = {0};
-    for (int64_t q = 0; q < n_part; ++q)
-      for (int r = 0; r < kStampRegions; ++r) tot[r] += (double)h[q * kStampRegions + r];
-    const char* names[kStampRegions] = {"plan", "cand", "shuffle_draws", "random_next", "decisions",
-                                        "trunc", "final_shuffle_draws", "fy_jacobi_passes_per_window"};
-    double all = 0;
-    for (int r = 0; r < kStampRegions - 1; ++r) all += tot[r];
-    fprintf(stderr, "[stamps] plan_replay_kernel mean cycles per partition:");
-    for (int r = 0; r < kStampRegions - 1; ++r)
-      fprintf(stderr, " %s=%.3g (%.1f%%)", names[r], tot[r] / n_part, 100.0 * tot[r] / (all + 1e-9));
-    fprintf(stderr, " %s=%.3f\n", names[kStampRegions - 1], tot[kStampRegions - 1] / n_part / 1e6);
-    // timeline (100 MHz real-time clock): partition durations and concurrency over the launch
-    std::vector<uint64_t> t(2 * n_part);
-    LDDL_HIP(hipMemcpyAsync(t.data(), d_tl, 16 * n_part, hipMemcpyDeviceToHost, st));
-    LDDL_HIP(hipStreamSynchronize(st));
-    uint64_t t0 = ~0ull, t1 = 0;
-    std::vector<double> dur(n_part);
-    for (int64_t q = 0; q < n_part; ++q) {
-      t0 = std::min(t0, t[2 * q]);
-      t1 = std::max(t1, t[2 * q + 1]);
-      dur[q] = (t[2 * q + 1] - t[2 * q]) / 1e5;  // ms
-    }
-    std::vector<double> sd = dur;
-    std::sort(sd.begin(), sd.end());
-    const double span = (t1 - t0) / 1e5;
-    fprintf(stderr, "[timeline] span %.2f ms, partition ms min %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f\n",
-            span, sd[0], sd[n_part / 10], sd[n_part / 2], sd[n_part * 9 / 10], sd[n_part - 1]);
-    const int nb = 40;
-    fprintf(stderr, "[timeline] active partitions per %.2f ms bin:", span / nb);
-    for (int b = 0; b < nb; ++b) {
-      const uint64_t a = t0 + (t1 - t0) * b / nb, e = t0 + (t1 - t0) * (b + 1) / nb;
-      double act = 0;  // partition-time inside the bin / bin length
-      for (int64_t q = 0; q < n_part; ++q) {
-        const uint64_t s0 = std::max(a, t[2 * q]), s1 = std::min(e, t[2 * q + 1]);
-        if (s1 > s0) act += (double)(s1 - s0);
-      }
-      fprintf(stderr, " %.0f", act / (double)(e - a));
-    }
-    fprintf(stderr, "\n[timeline] start ms of partitions by index decile:");
-    for (int k = 0; k <= 10; ++k) {
-      const int64_t q = std::min<int64_t>(n_part - 1, n_part * k / 10);
-      fprintf(stderr, " %.1f", (t[2 * q] - t0) / 1e5);
-    }
-    fprintf(stderr, "\n");
+// diagnostic build: region shares of plan_replay_kernel and the timeline of its partitions
+static int report_plan_stamps(const PlanWork& W) {
+  const int64_t n_part = W.n_part;
+  hipStream_t st = W.st;
+  std::vector<uint64_t> h(n_part * kStampRegions);
+  LDDL_HIP(hipMemcpyAsync(h.data(), W.d_stamps, 8 * h.size(), hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipStreamSynchronize(st));
+  double tot[kStampRegions] = {0};
+  for (int64_t q = 0; q < n_part; ++q)
+    for (int r = 0; r < kStampRegions; ++r) tot[r] += (double)h[q * kStampRegions + r];
+  const char* names[kStampRegions] = {"plan", "cand", "shuffle_draws", "random_next", "decisions",
+                                      "trunc", "final_shuffle_draws", "fy_jacobi_passes_per_window"};
+  double all = 0;
+  for (int r = 0; r < kStampRegions - 1; ++r) all += tot[r];
+  fprintf(stderr, "[stamps] plan_replay_kernel mean cycles per partition:");
+  for (int r = 0; r < kStampRegions - 1; ++r)
+    fprintf(stderr, " %s=%.3g (%.1f%%)", names[r], tot[r] / n_part, 100.0 * tot[r] / (all + 1e-9));
+  fprintf(stderr, " %s=%.3f\n", names[kStampRegions - 1], tot[kStampRegions - 1] / n_part / 1e6);
+  // timeline (100 MHz real-time clock): partition durations and concurrency over the launch
+  std::vector<uint64_t> t(2 * n_part);
+  LDDL_HIP(hipMemcpyAsync(t.data(), W.d_tl, 16 * n_part, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipStreamSynchronize(st));
+  uint64_t t0 = ~0ull, t1 = 0;
+  std::vector<double> dur(n_part);
+  for (int64_t q = 0; q < n_part; ++q) {
+    t0 = std::min(t0, t[2 * q]);
+    t1 = std::max(t1, t[2 * q + 1]);
+    dur[q] = (t[2 * q + 1] - t[2 * q]) / 1e5;  // ms
   }
+  std::vector<double> sd = dur;
+  std::sort(sd.begin(), sd.end());
+  const double span = (t1 - t0) / 1e5;
+  fprintf(stderr, "[timeline] span %.2f ms, partition ms min %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f\n",
+          span, sd[0], sd[n_part / 10], sd[n_part / 2], sd[n_part * 9 / 10], sd[n_part - 1]);
+  const int nb = 40;
+  fprintf(stderr, "[timeline] active partitions per %.2f ms bin:", span / nb);
+  for (int b = 0; b < nb; ++b) {
+    const uint64_t a = t0 + (t1 - t0) * b / nb, e = t0 + (t1 - t0) * (b + 1) / nb;
+    double act = 0;  // partition-time inside the bin / bin length
+    for (int64_t q = 0; q < n_part; ++q) {
+      const uint64_t s0 = std::max(a, t[2 * q]), s1 = std::min(e, t[2 * q + 1]);
+      if (s1 > s0) act += (double)(s1 - s0);
+    }
+    fprintf(stderr, " %.0f", act / (double)(e - a));
+  }
+  fprintf(stderr, "\n[timeline] start ms of partitions by index decile:");
+  for (int k = 0; k <= 10; ++k) {
+    const int64_t q = std::min<int64_t>(n_part - 1, n_part * k / 10);
+    fprintf(stderr, " %.1f", (t[2 * q] - t0) / 1e5);
+  }
+  fprintf(stderr, "\n");
+  return 0;
+}
 #endif
-  // layout (part_base and n_pairs came with the planner's sync). With masking, the mask replay
-  // (fy_resolve, planner order) also writes every pair's gather record at its output position
-  // and the two output-order scans follow; without, pair_prep builds the records from the
-  // output order. (Round 4 ran pair_prep beside fy_resolve on a second stream: 15.6 ms for the
-  // section, both kernels slowed by the other; the fused replay reads each slot record once.)
-  TRY(alloc_layout(P->n_pairs));
-  if (prm->masking) {
-    if (P->n_pairs) {
-      ResolveArgs RA{M.slots, P->n_pairs, P->desc, spool, jpool, P->mpos, P->kscan, P->dense, cls,
-                     sep, M.dstq, P->rec, pcnt, 0};
-      const dim3 grid((unsigned)((P->n_pairs + 63) / 64));
-      // a lane's column covers the padded draw region (steps up to nc rounded up to 16)
-      const size_t col = (size_t)((prm->seq + 15) & ~15);
-      RA.col_rows = (int32_t)col;
-      // Branch-free steps for long pairs (C3, seq 512: 77.6 -> 46.8 ms), the guarded ones at
-      // seq <= 131 (64 pairs per wave: 10.1 ms against 11.5 branch-free; profiles/r05k_*).
-      // A/B: LDDL_FY_MODE=0 / 1 forces one kind everywhere; LDDL_FY_LW=32: 32 pairs per wave at
-      // seq > 256 (50.7 ms)
-      const int fy_mode = getenv("LDDL_FY_MODE") ? atoi(getenv("LDDL_FY_MODE")) : -1;
-      const int fy_lw = getenv("LDDL_FY_LW") ? atoi(getenv("LDDL_FY_LW")) : 16;
-      // move-only groups at seq > 256 read one entry ahead (46.8 -> 44.4 ms; 2 ahead 45.9, 3 ahead
-      // 46.7: the forwarding selects grow; profiles/r05m_*). LDDL_FY_RA=0..3 (A/B)
-      const int fy_ra = getenv("LDDL_FY_RA") ? atoi(getenv("LDDL_FY_RA")) : 1;
-      // draw vectors (8 steps each) in flight per lane at seq > 256 (A/B: LDDL_FY_PF=2 / 8)
-      const int fy_pf = getenv("LDDL_FY_PF") ? atoi(getenv("LDDL_FY_PF")) : 4;
-      // the A/B knobs take only the values a test runs (unsupported values and
-      // combinations were ignored without notice)
-      if (fy_mode < -1 || fy_mode > 1) LDDL_FAIL(-1, "LDDL_FY_MODE must be 0 or 1");
-      if (fy_lw != 16 && fy_lw != 32) LDDL_FAIL(-1, "LDDL_FY_LW must be 16 or 32");
-      if (fy_ra < 0 || fy_ra > 3) LDDL_FAIL(-1, "LDDL_FY_RA must be 0 .. 3");
-      if (fy_pf != 2 && fy_pf != 4 && fy_pf != 8) LDDL_FAIL(-1, "LDDL_FY_PF must be 2, 4 or 8");
-      if (fy_pf != 4 && fy_ra != 1) LDDL_FAIL(-1, "LDDL_FY_PF applies with LDDL_FY_RA=1 only");
-      if ((fy_ra != 1 || fy_pf != 4) && (fy_mode == 0 || fy_lw == 32))
-        LDDL_FAIL(-1, "LDDL_FY_RA / PF select 16-lane branch-free variants (not with LDDL_FY_MODE=0 "
-                      "or LDDL_FY_LW=32)");
+
+// The mask replay (fy_resolve, planner order): every pair's mask positions, and its gather
+// record and counts at its output position.
+static int resolve_masks(lddl_pairs* P, PlanWork& W) {
+  if (!P->n_pairs) return 0;
+  const int32_t seq = P->seq;
+  const FyKnobs& fy = W.fy;
+  hipStream_t st = W.st;
+  ResolveArgs RA{W.M.slots, P->n_pairs, P->desc, W.spool, W.jpool, P->mpos, P->kscan, P->dense,
+                 P->cls_id, P->sep_id, W.M.dstq, P->rec, W.pcnt, 0};
+  // a lane's column covers the padded draw region (steps up to nc rounded up to 16)
+  const size_t col = (size_t)((seq + 15) & ~15);
+  RA.col_rows = (int32_t)col;
+  // Branch-free steps for long pairs (C3, seq 512: 77.6 -> 46.8 ms), the guarded ones at
+  // seq <= 131 (64 pairs per wave: 10.1 ms against 11.5 branch-free; profiles/r05k_*).
+  // A/B: LDDL_FY_MODE=0 / 1 forces one kind everywhere; LDDL_FY_LW=32: 32 pairs per wave at
+  // seq > 256 (50.7 ms)
+  // move-only groups at seq > 256 read one entry ahead (46.8 -> 44.4 ms; 2 ahead 45.9, 3 ahead
+  // 46.7: the forwarding selects grow; profiles/r05m_*). LDDL_FY_RA=0..3 (A/B)
+  // draw vectors (8 steps each) in flight per lane at seq > 256 (A/B: LDDL_FY_PF=2 / 8)
 #define LDDL_FY_LAUNCH(T, NG, LW, BF, ...)                                                     \
   hipLaunchKernelGGL((fy_resolve_kernel<T, T, NG, LW, BF, ##__VA_ARGS__>),                     \
                      dim3((unsigned)((P->n_pairs + LW - 1) / LW)), dim3(LW),                   \
                      (size_t)LW * sizeof(T) * col, st, RA)
-      if (prm->seq <= 131) {  // nc <= 128: all draws in registers (8 uint4 of 1-byte draws); 64
-        // pairs per wave (C2: 10.2 ms; 32 per wave 11.9, 16 per wave 20.1, profiles/r04slw_*)
-        if (fy_mode == 1) LDDL_FY_LAUNCH(uint8_t, 8, 64, true);
-        else LDDL_FY_LAUNCH(uint8_t, 8, 64, false);
-      // long pairs: 16 lanes (pairs) per wave (C3, seq 512: 106 ms with 64, 109 with 32, 93 with
-      // 16; profiles/r04fy_*)
-      } else if (prm->seq <= 256) {  // candidate indices, positions and draws fit a byte
-        if (fy_mode) LDDL_FY_LAUNCH(uint8_t, 0, 16, true);
-        else LDDL_FY_LAUNCH(uint8_t, 0, 16, false);
-      } else if (fy_lw == 32) {
-        if (fy_mode) LDDL_FY_LAUNCH(uint16_t, 0, 32, true);
-        else LDDL_FY_LAUNCH(uint16_t, 0, 32, false);
-      } else {
-        if (!fy_mode) LDDL_FY_LAUNCH(uint16_t, 0, 16, false);
-        else if (fy_ra == 1 && fy_pf == 8) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 1, 8);
-        else if (fy_ra == 1 && fy_pf == 2) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 1, 2);
-        else if (fy_ra == 1) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 1);
-        else if (fy_ra == 2) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 2);
-        else if (fy_ra == 3) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 3);
-        else LDDL_FY_LAUNCH(uint16_t, 0, 16, true);
-      }
-#undef LDDL_FY_LAUNCH
-    }
-    LDDL_HIP(hipGetLastError());
-    TRY(scan_only(st));
+  if (seq <= 131) {  // nc <= 128: all draws in registers (8 uint4 of 1-byte draws); 64
+    // pairs per wave (C2: 10.2 ms; 32 per wave 11.9, 16 per wave 20.1, profiles/r04slw_*)
+    if (fy.mode == 1) LDDL_FY_LAUNCH(uint8_t, 8, 64, true);
+    else LDDL_FY_LAUNCH(uint8_t, 8, 64, false);
+  // long pairs: 16 lanes (pairs) per wave (C3, seq 512: 106 ms with 64, 109 with 32, 93 with
+  // 16; profiles/r04fy_*)
+  } else if (seq <= 256) {  // candidate indices, positions and draws fit a byte
+    if (fy.mode) LDDL_FY_LAUNCH(uint8_t, 0, 16, true);
+    else LDDL_FY_LAUNCH(uint8_t, 0, 16, false);
+  } else if (fy.lw == 32) {
+    if (fy.mode) LDDL_FY_LAUNCH(uint16_t, 0, 32, true);
+    else LDDL_FY_LAUNCH(uint16_t, 0, 32, false);
   } else {
-    TRY(prep_and_scan(st));
+    if (!fy.mode) LDDL_FY_LAUNCH(uint16_t, 0, 16, false);
+    else if (fy.ra == 1 && fy.pf == 8) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 1, 8);
+    else if (fy.ra == 1 && fy.pf == 2) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 1, 2);
+    else if (fy.ra == 1) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 1);
+    else if (fy.ra == 2) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 2);
+    else if (fy.ra == 3) LDDL_FY_LAUNCH(uint16_t, 0, 16, true, 3);
+    else LDDL_FY_LAUNCH(uint16_t, 0, 16, true);
   }
-  }  // replay
+#undef LDDL_FY_LAUNCH
+  return 0;
+}
+
+// Layout of a replay plan (part_base and n_pairs came with the planner's sync). With masking, the
+// mask replay also writes every pair's gather record at its output position and the two
+// output-order scans follow; without, pair_prep builds the records from the output order.
+// (Round 4 ran pair_prep beside fy_resolve on a second stream: 15.6 ms for the section, both
+// kernels slowed by the other; the fused replay reads each slot record once.)
+static int layout_replay(lddl_pairs* P, PlanWork& W) {
+  if (!P->masking) return layout_pairs(P, W);
+  int rc;
+  if ((rc = layout_alloc(P, W)) || (rc = resolve_masks(P, W))) return rc;
+  LDDL_HIP(hipGetLastError());
+  return layout_scan(P, W);
+}
+
+static int32_t max_predictions(const lddl_pair_params* prm) {
+  if (!prm->masking) return 0;
+  const int32_t m = (int32_t)rint((double)prm->seq * prm->masked_lm_ratio);
+  return std::min(std::max(m, 1), prm->seq);
+}
+
+extern "C" int lddl_pairs_plan(lddl_ctx* c, void* stream, const lddl_pair_params* prm,
+                               const int64_t* d_sent_off, const int32_t* d_ids,
+                               const int32_t* d_sent_len, int64_t n_sent,
+                               const int64_t* d_doc_sent_off, int64_t n_doc,
+                               const int64_t* d_part_doc_off, const int64_t* d_part_seed,
+                               int64_t n_part, lddl_pairs** out, int64_t* counts) {
+  *out = nullptr;
+  FyKnobs fy;
+  int rc;
+  if ((rc = check_plan_args(c, prm, &fy))) return rc;
+  hipStream_t st = as_stream(stream);
+  // until it is handed out, an error return drops the plan: its blocks go back on `st`
+  std::unique_ptr<lddl_pairs> P(new lddl_pairs(&c->arena, st));
+  P->n_part = n_part;
+  P->masking = prm->masking;
+  P->seq = prm->seq;
+  P->cls_id = c->tab.special_id[kCls];
+  P->sep_id = c->tab.special_id[kSep];
+  P->max_pred = max_predictions(prm);
+  LDDL_HIP(hipEventCreate(&P->ev[0]));
+  LDDL_HIP(hipEventCreate(&P->ev[1]));
+  PlanWork W{c, prm, d_ids, d_part_seed, n_sent, n_part, st, P->mem, fy};
+  if ((rc = compact_inputs(P.get(), W, d_sent_off, d_sent_len, d_doc_sent_off, n_doc, d_part_doc_off)))
+    return rc;
   if (prm->rng == LDDL_RNG_NATIVE) {
-    TRY(alloc_layout(P->n_pairs));
-    TRY(prep_and_scan(st));
+    if ((rc = plan_native(P.get(), W))) return rc;
+  } else {
+    if ((rc = plan_replay(P.get(), W)) || (rc = shuffle_partitions(P.get(), W))) return rc;
+#ifdef LDDL_STAMPS
+    if ((rc = report_plan_stamps(W))) return rc;
+#endif
+    if ((rc = layout_replay(P.get(), W))) return rc;
   }
   LDDL_HIP(hipMemcpyAsync(&P->n_tokens, P->tok_off + P->n_pairs, 8, hipMemcpyDeviceToHost, st));
   if (prm->masking)
@@ -2839,7 +2881,7 @@ extern "C" int lddl_pairs_plan(lddl_ctx* c, void* stream, const lddl_pair_params
     counts[3] = P->n_kept_sent;
     counts[4] = P->n_kept_doc;
   }
-  *out = P;
+  *out = P.release();
   return 0;
 }
 
@@ -2888,7 +2930,7 @@ extern "C" int lddl_pairs_emit(lddl_pairs* P, void* stream, void* d_tokens, int6
 
 extern "C" int lddl_pairs_destroy(lddl_pairs* P, void* stream) {
   if (!P) return 0;
-  P->release(as_stream(stream));
+  P->mem.release(as_stream(stream));  // (the last use of the blocks was on this stream)
   delete P;
   return 0;
 }

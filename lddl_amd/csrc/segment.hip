@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 
 #include "common.h"
 #include "ctx.h"
@@ -668,6 +669,17 @@ __global__ void segment_fill_kernel(const int64_t* __restrict__ doc_off, int64_t
 
 using namespace lddl;
 
+// What lddl_segment_count leaves for lddl_segment_fill. The scope owns every block: dropping the
+// object gives them back to the arena (on the counting stream unless released on another).
+struct PendingSeg {
+  ArenaScope mem;
+  int32_t *cand = nullptr, *ccnt = nullptr, *rs_rel = nullptr, *cnt = nullptr, *fdoc = nullptr;
+  int64_t *coff = nullptr, *dso = nullptr, *scratch = nullptr, *fq = nullptr, *fbound = nullptr;
+  const int64_t* doc_off = nullptr;
+  int64_t n_doc = 0;
+  PendingSeg(DevArena* arena, hipStream_t st) : mem(arena, st) {}
+};
+
 struct lddl_punkt_state {
   uint16_t* l1 = nullptr;
   uint8_t* pages = nullptr;
@@ -677,14 +689,8 @@ struct lddl_punkt_state {
   uint32_t hmask = 0;
   int32_t n_rec = 0;
   uint8_t* keys = nullptr;
-  // pending segmentation (between lddl_segment_count and lddl_segment_fill)
-  DevArena::Block cand, ccnt, rs_rel, coff, fq, fdoc, fbound, cnt, dso, scratch;
-  const int64_t* doc_off = nullptr;
-  int64_t n_doc = -1;
-  int64_t n_sent = 0;
-  std::vector<DevArena::Block*> blocks() {
-    return {&cand, &ccnt, &rs_rel, &coff, &fq, &fdoc, &fbound, &cnt, &dso, &scratch};
-  }
+  // the segmentation between lddl_segment_count and lddl_segment_fill (null: none pending)
+  std::unique_ptr<PendingSeg> pending;
   void free_tables() {
     (void)hipFree(l1);
     (void)hipFree(pages);
@@ -708,9 +714,7 @@ extern "C" void lddl_punkt_release(lddl_ctx* c) {
   if (!p) return;
   (void)hipDeviceSynchronize();
   p->free_tables();
-  for (DevArena::Block* b : p->blocks())
-    if (b->p) (void)hipFree(b->p);
-  delete p;
+  delete p;  // (a pending segmentation's blocks go back to the arena)
   c->punkt = nullptr;
 }
 
@@ -798,97 +802,75 @@ extern "C" int lddl_segment_count(lddl_ctx* c, void* stream, const uint8_t* d_te
   lddl_punkt_state* ps = punkt_of(c);
   if (!ps || !ps->l1) LDDL_FAIL(-1, "Punkt parameters not set (lddl_punkt_set_params)");
   if (n_doc < 0 || n_bytes < 0 || !n_sent) LDDL_FAIL(-1, "bad sizes");
-  if (ps->n_doc >= 0) LDDL_FAIL(-1, "a segmentation is pending: call lddl_segment_fill first");
+  if (ps->pending) LDDL_FAIL(-1, "a segmentation is pending: call lddl_segment_fill first");
   hipStream_t st = as_stream(stream);
-  DevArena& A = c->arena;
-  const size_t nd = (size_t)n_doc + 1;
-  LDDL_HIP(A.take(sizeof(int32_t) * (size_t)(n_bytes / 2 + n_doc + 2), st, ps->cand));
-  LDDL_HIP(A.take(sizeof(int32_t) * nd, st, ps->ccnt));
-  LDDL_HIP(A.take(sizeof(int32_t) * nd, st, ps->rs_rel));
-  LDDL_HIP(A.take(sizeof(int32_t) * nd, st, ps->cnt));
-  LDDL_HIP(A.take(sizeof(int64_t) * nd, st, ps->coff));
-  LDDL_HIP(A.take(sizeof(int64_t) * nd, st, ps->dso));
-  LDDL_HIP(A.take(sizeof(int64_t) * (size_t)scan_scratch_elems(n_doc), st, ps->scratch));
+  // local until the count is complete: an error return gives the blocks back
+  auto S = std::make_unique<PendingSeg>(&c->arena, st);
+  const int64_t nd = n_doc + 1;
+  int rc;
+  if ((rc = S->mem.take(&S->cand, n_bytes / 2 + n_doc + 2)) || (rc = S->mem.take(&S->ccnt, nd)) ||
+      (rc = S->mem.take(&S->rs_rel, nd)) || (rc = S->mem.take(&S->cnt, nd)) ||
+      (rc = S->mem.take(&S->coff, nd)) || (rc = S->mem.take(&S->dso, nd)) ||
+      (rc = S->mem.take(&S->scratch, scan_scratch_elems(n_doc))))
+    return rc;
   PunktTab t{ps->l1, ps->pages, ps->lower, ps->n_lower, ps->hash, ps->hmask, ps->n_rec, ps->keys};
-  int32_t* ccnt = static_cast<int32_t*>(ps->ccnt.p);
-  int32_t* cnt = static_cast<int32_t*>(ps->cnt.p);
-  int64_t* coff = static_cast<int64_t*>(ps->coff.p);
-  int64_t* dso = static_cast<int64_t*>(ps->dso.p);
-  int64_t* scratch = static_cast<int64_t*>(ps->scratch.p);
   const int64_t dgrid = std::max<int64_t>(1, (n_doc + kSegWaves - 1) / kSegWaves);
   if (n_doc > 0) {
     hipLaunchKernelGGL(segment_classify_kernel, dim3((unsigned)dgrid), dim3(64 * kSegWaves), 0, st, t, d_text,
-                       n_bytes, d_doc_off, n_doc, static_cast<int32_t*>(ps->cand.p), ccnt,
-                       static_cast<int32_t*>(ps->rs_rel.p), cnt);
+                       n_bytes, d_doc_off, n_doc, S->cand, S->ccnt, S->rs_rel, S->cnt);
     LDDL_HIP(hipGetLastError());
   }
-  LDDL_HIP(scan_exclusive(CntAt{ccnt}, n_doc, coff, scratch, st));
+  LDDL_HIP(scan_exclusive(CntAt{S->ccnt}, n_doc, S->coff, S->scratch, st));
   int64_t n_cand = 0;
-  LDDL_HIP(hipMemcpyAsync(&n_cand, coff + n_doc, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipMemcpyAsync(&n_cand, S->coff + n_doc, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   LDDL_HIP(hipStreamSynchronize(st));
-  const size_t ncap = (size_t)std::max<int64_t>(n_cand, 1);
-  LDDL_HIP(A.take(sizeof(int64_t) * ncap, st, ps->fq));
-  LDDL_HIP(A.take(sizeof(int32_t) * ncap, st, ps->fdoc));
-  LDDL_HIP(A.take(sizeof(int64_t) * ncap, st, ps->fbound));
+  if ((rc = S->mem.take(&S->fq, n_cand)) || (rc = S->mem.take(&S->fdoc, n_cand)) ||
+      (rc = S->mem.take(&S->fbound, n_cand)))
+    return rc;
   if (n_cand > 0) {
     hipLaunchKernelGGL(segment_flatten_kernel, dim3((unsigned)dgrid), dim3(64 * kSegWaves), 0, st, d_doc_off,
-                       n_doc, static_cast<const int32_t*>(ps->cand.p), coff, static_cast<int64_t*>(ps->fq.p),
-                       static_cast<int32_t*>(ps->fdoc.p));
+                       n_doc, (const int32_t*)S->cand, S->coff, S->fq, S->fdoc);
     const int64_t egrid = (n_cand + kEvalBlock - 1) / kEvalBlock;
-    if (ps->n_rec)
-      hipLaunchKernelGGL(segment_eval_kernel<true>, dim3((unsigned)egrid), dim3(kEvalBlock), 0, st, t, d_text,
-                         n_bytes, d_doc_off, static_cast<const int32_t*>(ps->rs_rel.p),
-                         static_cast<const int64_t*>(ps->fq.p), static_cast<const int32_t*>(ps->fdoc.p), n_cand,
-                         static_cast<int64_t*>(ps->fbound.p), cnt);
-    else
-      hipLaunchKernelGGL(segment_eval_kernel<false>, dim3((unsigned)egrid), dim3(kEvalBlock), 0, st, t, d_text,
-                         n_bytes, d_doc_off, static_cast<const int32_t*>(ps->rs_rel.p),
-                         static_cast<const int64_t*>(ps->fq.p), static_cast<const int32_t*>(ps->fdoc.p), n_cand,
-                         static_cast<int64_t*>(ps->fbound.p), cnt);
+    auto eval = ps->n_rec ? segment_eval_kernel<true> : segment_eval_kernel<false>;  // (trained parameters?)
+    hipLaunchKernelGGL(eval, dim3((unsigned)egrid), dim3(kEvalBlock), 0, st, t, d_text, n_bytes, d_doc_off,
+                       (const int32_t*)S->rs_rel, (const int64_t*)S->fq, (const int32_t*)S->fdoc, n_cand,
+                       S->fbound, S->cnt);
     LDDL_HIP(hipGetLastError());
   }
-  LDDL_HIP(scan_exclusive(CntAt{cnt}, n_doc, dso, scratch, st));
-  LDDL_HIP(hipMemcpyAsync(&ps->n_sent, dso + n_doc, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  LDDL_HIP(scan_exclusive(CntAt{S->cnt}, n_doc, S->dso, S->scratch, st));
+  LDDL_HIP(hipMemcpyAsync(n_sent, S->dso + n_doc, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   LDDL_HIP(hipStreamSynchronize(st));
-  ps->doc_off = d_doc_off;
-  ps->n_doc = n_doc;
-  *n_sent = ps->n_sent;
+  S->doc_off = d_doc_off;
+  S->n_doc = n_doc;
+  ps->pending = std::move(S);
   return 0;
 }
 
 extern "C" int lddl_segment_fill(lddl_ctx* c, void* stream, int64_t* d_sent_off, int64_t* d_doc_sent_off) {
   if (!c) LDDL_FAIL(-1, "null ctx");
   lddl_punkt_state* ps = punkt_of(c);
-  if (!ps || ps->n_doc < 0) LDDL_FAIL(-1, "no pending segmentation (lddl_segment_count)");
+  if (!ps || !ps->pending) LDDL_FAIL(-1, "no pending segmentation (lddl_segment_count)");
+  if (!d_sent_off != !d_doc_sent_off) LDDL_FAIL(-1, "lddl_segment_fill: null output");
   hipStream_t st = as_stream(stream);
-  if (!d_sent_off && !d_doc_sent_off) {  // cancel: release the pending segmentation's scratch
-    for (DevArena::Block* b : ps->blocks()) {
-      c->arena.give(*b, st);
-      *b = DevArena::Block{};
-    }
-    ps->n_doc = -1;
-    return 0;
-  }
-  if (!d_sent_off || !d_doc_sent_off) LDDL_FAIL(-1, "lddl_segment_fill: null output");
-  const int64_t n_doc = ps->n_doc;
+  // the call ends the pending segmentation, whatever it returns (both outputs null: cancel)
+  std::unique_ptr<PendingSeg> S = std::move(ps->pending);
   int rc = 0;
-  if (n_doc > 0) {
-    const int64_t grid = (n_doc + 3) / 4;
-    hipLaunchKernelGGL(segment_fill_kernel, dim3((unsigned)grid), dim3(256), 0, st, ps->doc_off, n_doc,
-                       static_cast<const int64_t*>(ps->coff.p), static_cast<const int64_t*>(ps->fbound.p),
-                       static_cast<const int64_t*>(ps->dso.p), d_sent_off);
-  } else {
-    if (hipMemsetAsync(d_sent_off, 0, sizeof(int64_t), st) != hipSuccess) rc = -100;
+  if (d_sent_off) {
+    const int64_t n_doc = S->n_doc;
+    if (n_doc > 0) {
+      const int64_t grid = (n_doc + 3) / 4;
+      hipLaunchKernelGGL(segment_fill_kernel, dim3((unsigned)grid), dim3(256), 0, st, S->doc_off, n_doc,
+                         (const int64_t*)S->coff, (const int64_t*)S->fbound, (const int64_t*)S->dso,
+                         d_sent_off);
+    } else {
+      if (hipMemsetAsync(d_sent_off, 0, sizeof(int64_t), st) != hipSuccess) rc = -100;
+    }
+    if (hipMemcpyAsync(d_doc_sent_off, S->dso, sizeof(int64_t) * (size_t)(n_doc + 1), hipMemcpyDeviceToDevice,
+                       st) != hipSuccess)
+      rc = -100;
+    if (hipGetLastError() != hipSuccess) rc = -100;
   }
-  if (hipMemcpyAsync(d_doc_sent_off, ps->dso.p, sizeof(int64_t) * (size_t)(n_doc + 1), hipMemcpyDeviceToDevice,
-                     st) != hipSuccess)
-    rc = -100;
-  if (hipGetLastError() != hipSuccess) rc = -100;
-  for (DevArena::Block* b : ps->blocks()) {
-    c->arena.give(*b, st);
-    *b = DevArena::Block{};
-  }
-  ps->n_doc = -1;
+  S->mem.release(st);
   if (rc) LDDL_FAIL(rc, "lddl_segment_fill: HIP launch/copy failed");
   return 0;
 }

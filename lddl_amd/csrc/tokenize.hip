@@ -1388,6 +1388,135 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
 
 using namespace lddl;
 
+constexpr int kFbHead = 1;  // fallback list: [0] = count, then sentence indices
+
+// The arguments of one lddl_tokenize call, as its launches share them.
+struct TokCall {
+  lddl_ctx* c;
+  hipStream_t st;
+  const uint8_t* d_text;
+  int64_t n_bytes;
+  const int64_t* d_sent_off;
+  int64_t n_sent;
+  int32_t max_pieces;
+  int32_t* d_ids;
+  int32_t* d_sent_len;
+  int32_t* fb = nullptr;         // the fallback list
+  int32_t* chunk_ctr = nullptr;  // the batch kernel's chunk counter (after the list)
+  int64_t n_cu = 256;
+  int64_t grid = 0;  // workgroups of the last streaming launch
+};
+
+// The lane kernel over sentences [s0, s0 + n): those on the fallback list, or all of them
+// (whole) on a grid of at most grid_cap workgroups.
+static int launch_lane(const TokCall& T, int64_t s0, int64_t n, int64_t grid_cap, bool whole) {
+  const int64_t grid = std::min<int64_t>((n + kBlock - 1) / kBlock, grid_cap);
+  hipLaunchKernelGGL(tokenize_lane_kernel, dim3((unsigned)grid), dim3(kBlock), 0, T.st, T.c->tab,
+                     T.d_text, T.d_sent_off + s0, n, T.max_pieces, T.d_ids, T.d_sent_len + s0,
+                     whole ? nullptr : T.fb + kFbHead,
+                     whole ? nullptr : reinterpret_cast<const uint32_t*>(T.fb));
+  LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
+// diagnostics: one sentence per wavefront, no batching; then its fallback list
+static int tokenize_wave(const TokCall& T) {
+  int per_cu = 0;
+  LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tokenize_wave_kernel, 64 * kTW, 0));
+  const int64_t want = (T.n_sent + kTW - 1) / kTW;
+  const int64_t grid = std::min<int64_t>(want, T.n_cu * std::max(per_cu, 1));
+  hipLaunchKernelGGL(tokenize_wave_kernel, dim3((unsigned)grid), dim3(64 * kTW), 0, T.st, T.c->tab,
+                     T.d_text, T.n_bytes, T.d_sent_off, T.n_sent, T.max_pieces, T.d_ids, T.d_sent_len,
+                     T.fb + kFbHead, reinterpret_cast<uint32_t*>(T.fb));
+  return launch_lane(T, 0, T.n_sent, T.n_cu * 2, false);
+}
+
+// One launch of the streaming kernel over sentences [s0, s0 + n) (the sentence offsets are
+// absolute, so a sub-range is a pointer offset), then the lane kernel for its fallback list.
+// grid_max: the resident workgroups (grid-stride over sentences with exactly those: a second
+// wave of workgroups would start only when the first finished, a 2x tail).
+static int batch_pass(TokCall& T, int64_t grid_max, int64_t s0, int64_t n, int memo, WordMemo M) {
+  const int64_t want = (n + 16 * kBW - 1) / (16 * kBW);
+  int64_t grid = std::max<int64_t>(1, std::min<int64_t>(want, grid_max));
+  // tests: a smaller grid makes small inputs take the dynamic chunk claims
+  if (const char* g = getenv("LDDL_TOKENIZE_GRID")) grid = std::max<int64_t>(1, std::min<int64_t>(grid, atoll(g)));
+  T.grid = grid;
+  // the first grid x kBW chunks are taken statically (chunk w by wave w)
+  const int64_t first = std::min<int64_t>(grid * kBW * kChunk, (int64_t)INT32_MAX);
+  LDDL_HIP(hipMemsetAsync(T.fb, 0, sizeof(int32_t) * kFbHead, T.st));
+  LDDL_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.chunk_ctr), (int)first, 1, T.st));
+  const void* kfn = memo == kMemoBuild ? (const void*)tokenize_batch_kernel<kMemoBuild>
+                  : memo == kMemoLookup ? (const void*)tokenize_batch_kernel<kMemoLookup>
+                                        : (const void*)tokenize_batch_kernel<kMemoOff>;
+  const int64_t* so = T.d_sent_off + s0;
+  int32_t* sl = T.d_sent_len + s0;
+  int32_t* fl = T.fb + kFbHead;
+  uint32_t* fn = reinterpret_cast<uint32_t*>(T.fb);
+  void* args[] = {&T.c->tab, (void*)&T.d_text, &T.n_bytes, (void*)&so, &n, &T.max_pieces, &T.d_ids, &sl,
+                  &fl, &fn, &T.chunk_ctr, &M};
+  LDDL_HIP(hipLaunchKernel(kfn, dim3((unsigned)grid), dim3(64 * kBW), args, 0, T.st));
+  return launch_lane(T, s0, n, T.n_cu * 2, false);
+}
+
+#ifdef LDDL_STAMPS
+// diagnostic build: the streaming kernel's wave timeline (tl) and region counters (rg)
+static int stamps_begin(ArenaScope& diag, const TokCall& T, int64_t grid_max, unsigned long long** tl,
+                        unsigned long long** rg) {
+  int rc;
+  if ((rc = diag.take(tl, 2 * grid_max * kBW)) || (rc = diag.take(rg, kTokRegions + 10))) return rc;
+  LDDL_HIP(hipMemsetAsync(*tl, 0, 16 * grid_max * kBW, T.st));
+  LDDL_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tok_tl), tl, sizeof(*tl), 0, hipMemcpyHostToDevice, T.st));
+  LDDL_HIP(hipMemsetAsync(*rg, 0, 8 * (kTokRegions + 10), T.st));
+  LDDL_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tok_reg), rg, sizeof(*rg), 0, hipMemcpyHostToDevice, T.st));
+  return 0;
+}
+
+static int report_tok_stamps(const TokCall& T, const unsigned long long* tl, const unsigned long long* rg) {
+  // wave timeline (100 MHz real-time clock)
+  const int64_t nw = T.grid * kBW;
+  std::vector<unsigned long long> t(2 * nw);
+  LDDL_HIP(hipMemcpyAsync(t.data(), tl, 16 * nw, hipMemcpyDeviceToHost, T.st));
+  LDDL_HIP(hipStreamSynchronize(T.st));
+  unsigned long long t0 = ~0ull, t1 = 0;
+  std::vector<double> e(nw);
+  for (int64_t q = 0; q < nw; ++q) {
+    t0 = std::min(t0, t[2 * q]);
+    t1 = std::max(t1, t[2 * q + 1]);
+  }
+  for (int64_t q = 0; q < nw; ++q) e[q] = (t[2 * q + 1] - t0) / 1e5;
+  std::sort(e.begin(), e.end());
+  const double span = (t1 - t0) / 1e5;
+  fprintf(stderr, "[tok timeline] span %.2f ms, wave end ms: min %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f\n",
+          span, e[0], e[nw / 10], e[nw / 2], e[nw * 9 / 10], e[nw - 1]);
+  const int nb = 40;
+  fprintf(stderr, "[tok timeline] waves alive per %.2f ms bin:", span / nb);
+  for (int b = 0; b < nb; ++b) {
+    const double te = span * (b + 0.5) / nb;
+    int64_t alive = 0;
+    for (int64_t q = 0; q < nw; ++q) alive += e[q] > te;
+    fprintf(stderr, " %lld", (long long)alive);
+  }
+  fprintf(stderr, "\n");
+  unsigned long long r[kTokRegions + 10];
+  LDDL_HIP(hipMemcpy(r, rg, sizeof r, hipMemcpyDeviceToHost));
+  const unsigned long long* k = r + kTokRegions;
+  fprintf(stderr,
+          "[tok phaseB] flushes %llu units %llu | passes %llu lanes/pass %.1f | piece-steps: wave %llu "
+          "lane %llu (lane util %.2f) | bloom iters: wave %llu lane-useful %llu (util %.2f, per wave "
+          "step %.1f) | probe trips: wave %llu lane %llu (util %.2f)\n",
+          k[8], k[9], k[0], (double)k[1] / (k[0] ? k[0] : 1), k[2], k[3],
+          (double)k[3] / (64.0 * (k[2] ? k[2] : 1)), k[4], k[5], (double)k[5] / (64.0 * (k[4] ? k[4] : 1)),
+          (double)k[4] / (k[2] ? k[2] : 1), k[6], k[7], (double)k[7] / (64.0 * (k[6] ? k[6] : 1)));
+  unsigned long long tot = 0;
+  for (int q = 0; q < kTokRegions; ++q) tot += r[q];
+  static const char* names[kTokRegions] = {"banks", "phaseA", "phaseB", "place", "qshift", "chunk"};
+  fprintf(stderr, "[tok regions] wave-cycle shares:");
+  for (int q = 0; q < kTokRegions; ++q) fprintf(stderr, " %s %.1f%%", names[q], 100.0 * r[q] / (tot ? tot : 1));
+  fprintf(stderr, "\n");
+  return 0;
+}
+#endif
+
 extern "C" int lddl_tokenize(lddl_ctx* c, void* stream, const uint8_t* d_text, int64_t n_bytes,
                              const int64_t* d_sent_off, int64_t n_sent, int32_t max_pieces,
                              int32_t* d_ids, int32_t* d_sent_len) {
@@ -1397,164 +1526,58 @@ extern "C" int lddl_tokenize(lddl_ctx* c, void* stream, const uint8_t* d_text, i
   if (n_sent >= (int64_t)INT32_MAX - (1 << 22)) LDDL_FAIL(-1, "too many sentences in one call (%lld)", (long long)n_sent);
   if (n_sent == 0) return 0;
   hipStream_t st = as_stream(stream);
+  TokCall T{c, st, d_text, n_bytes, d_sent_off, n_sent, max_pieces, d_ids, d_sent_len};
   // diagnostics (each run by tests/test_tokenize_gpu.py against the oracle): "lane" = the
   // fallback kernel for the whole input, "wave" = one sentence per wavefront, "fused" = the
   // default, "plain" = the streaming kernel without the word memo. (Round 6's split form — phase B and placement in launches of their own — measured
   // slower and lives on branch ab/tok-split)
   const char* path = getenv("LDDL_TOKENIZE_PATH");
-  if (path && !strcmp(path, "lane")) {
-    const int64_t grid = std::min<int64_t>((n_sent + kBlock - 1) / kBlock, 65536);
-    hipLaunchKernelGGL(tokenize_lane_kernel, dim3((unsigned)grid), dim3(kBlock), 0, st, c->tab,
-                       d_text, d_sent_off, n_sent, max_pieces, d_ids, d_sent_len, nullptr, nullptr);
-    LDDL_HIP(hipGetLastError());
-    return 0;
-  }
+  if (path && !strcmp(path, "lane")) return launch_lane(T, 0, n_sent, 65536, true);
   if (path && strcmp(path, "wave") && strcmp(path, "fused") && strcmp(path, "plain"))
     LDDL_FAIL(-1, "LDDL_TOKENIZE_PATH must be lane, wave, fused or plain (got %s)", path);
-  // fallback list: [0] = count, then sentence indices
-  constexpr int kFbHead = 1;
-  DevArena::Block fbb;
-  // + the batch kernel's chunk counter after the list
-  LDDL_HIP(c->arena.take(sizeof(int32_t) * (size_t)(n_sent + kFbHead + 1), st, fbb));
-  int32_t* fb = static_cast<int32_t*>(fbb.p);
-  int32_t* chunk_ctr = fb + kFbHead + n_sent;
-  LDDL_HIP(hipMemsetAsync(fb, 0, sizeof(int32_t) * kFbHead, st));
+  ArenaTmp fbb(&c->arena, st);
+  LDDL_HIP(fbb.take(sizeof(int32_t) * (size_t)(n_sent + kFbHead + 1)));
+  T.fb = fbb.as<int32_t>();
+  T.chunk_ctr = T.fb + kFbHead + n_sent;
+  LDDL_HIP(hipMemsetAsync(T.fb, 0, sizeof(int32_t) * kFbHead, st));
   int n_cu = 256;
   (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-  // grid-stride over sentences with exactly the resident workgroups (a second wave of
-  // workgroups would start only when the first finished: a 2x tail)
+  T.n_cu = n_cu;
+  if (path && !strcmp(path, "wave")) return tokenize_wave(T);
   int per_cu = 0;
-  if (path && !strcmp(path, "wave")) {  // diagnostics: one sentence per wavefront, no batching
-    LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tokenize_wave_kernel, 64 * kTW, 0));
-    const int64_t want = (n_sent + kTW - 1) / kTW;
-    const int64_t grid = std::min<int64_t>(want, (int64_t)n_cu * std::max(per_cu, 1));
-    hipLaunchKernelGGL(tokenize_wave_kernel, dim3((unsigned)grid), dim3(64 * kTW), 0, st, c->tab,
-                       d_text, n_bytes, d_sent_off, n_sent, max_pieces, d_ids, d_sent_len, fb + kFbHead,
-                       reinterpret_cast<uint32_t*>(fb));
+  LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tokenize_batch_kernel<kMemoOff>, 64 * kBW, 0));
+  const int64_t grid_max = T.n_cu * std::max(per_cu, 1);
+  int rc;
+#ifdef LDDL_STAMPS
+  ArenaScope diag(&c->arena, st);
+  unsigned long long *tl, *rg;
+  if ((rc = stamps_begin(diag, T, grid_max, &tl, &rg))) return rc;
+#endif
+  // the word memo (above): a leading sample of 1/32 of the sentences (at least kMemoMinSample)
+  // builds it, the rest reads it. Off for vocabs whose ids do not fit 16 bits, for inputs too
+  // small to repay the second launch, and with LDDL_TOKENIZE_PATH=plain.
+  constexpr int64_t kMemoMinSample = 1 << 14;
+  int64_t n_sample = std::max<int64_t>(n_sent / kMemoDiv, kMemoMinSample);
+  bool memo = c->vocab_size <= 65536 && n_sent >= 4 * kMemoMinSample;
+  if (const char* e = getenv("LDDL_TOKENIZE_MEMO_SAMPLE")) {  // tests: the memo on small inputs
+    n_sample = atoll(e);
+    memo = c->vocab_size <= 65536 && n_sample > 0 && n_sample < n_sent;
+  }
+  if (path && !strcmp(path, "plain")) memo = false;
+  if (!memo) {
+    if ((rc = batch_pass(T, grid_max, 0, n_sent, kMemoOff, WordMemo{nullptr, 0}))) return rc;
   } else {
-    const int wpb = kBW;  // waves per workgroup
-    LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tokenize_batch_kernel<kMemoOff>, 64 * wpb, 0));
-#ifdef LDDL_STAMPS
-    const int64_t grid_max = (int64_t)n_cu * std::max(per_cu, 1);
-    unsigned long long* tl = nullptr;
-    unsigned long long* rg = nullptr;
-    LDDL_HIP(hipMalloc(&tl, 16 * grid_max * wpb));
-    LDDL_HIP(hipMemsetAsync(tl, 0, 16 * grid_max * wpb, st));
-    LDDL_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tok_tl), &tl, sizeof(tl), 0, hipMemcpyHostToDevice, st));
-    LDDL_HIP(hipMalloc(&rg, 8 * (kTokRegions + 10)));
-    LDDL_HIP(hipMemsetAsync(rg, 0, 8 * (kTokRegions + 10), st));
-    LDDL_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tok_reg), &rg, sizeof(rg), 0, hipMemcpyHostToDevice, st));
-#endif
-    int64_t grid = 0;
-    // one launch of the streaming kernel over sentences [s0, s0 + n) (the sentence offsets are
-    // absolute, so a sub-range is a pointer offset), then the lane kernel for its fallback list
-    auto pass = [&](int64_t s0, int64_t n, int memo, WordMemo M) -> int {
-      const int64_t want = (n + 16 * wpb - 1) / (16 * wpb);
-      grid = std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)n_cu * std::max(per_cu, 1)));
-      // tests: a smaller grid makes small inputs take the dynamic chunk claims
-      if (const char* g = getenv("LDDL_TOKENIZE_GRID")) grid = std::max<int64_t>(1, std::min<int64_t>(grid, atoll(g)));
-      // the first grid x wpb chunks are taken statically (chunk w by wave w)
-      const int64_t first = std::min<int64_t>(grid * wpb * kChunk, (int64_t)INT32_MAX);
-      LDDL_HIP(hipMemsetAsync(fb, 0, sizeof(int32_t) * kFbHead, st));
-      LDDL_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(chunk_ctr), (int)first, 1, st));
-      const void* kfn = memo == kMemoBuild ? (const void*)tokenize_batch_kernel<kMemoBuild>
-                      : memo == kMemoLookup ? (const void*)tokenize_batch_kernel<kMemoLookup>
-                                            : (const void*)tokenize_batch_kernel<kMemoOff>;
-      const int64_t* so = d_sent_off + s0;
-      int32_t* sl = d_sent_len + s0;
-      int32_t* fl = fb + kFbHead;
-      uint32_t* fn = reinterpret_cast<uint32_t*>(fb);
-      void* args[] = {&c->tab, (void*)&d_text, &n_bytes, (void*)&so, &n, &max_pieces, &d_ids, &sl,
-                      &fl, &fn, &chunk_ctr, &M};
-      LDDL_HIP(hipLaunchKernel(kfn, dim3((unsigned)grid), dim3(64 * kBW), args, 0, st));
-      const int64_t fgrid = std::min<int64_t>((n + kBlock - 1) / kBlock, (int64_t)n_cu * 2);
-      hipLaunchKernelGGL(tokenize_lane_kernel, dim3((unsigned)fgrid), dim3(kBlock), 0, st, c->tab,
-                         d_text, so, n, max_pieces, d_ids, sl, fl, reinterpret_cast<const uint32_t*>(fb));
-      LDDL_HIP(hipGetLastError());
-      return 0;
-    };
-    // the word memo (above): a leading sample of 1/32 of the sentences (at least kMemoMinSample)
-    // builds it, the rest reads it. Off for vocabs whose ids do not fit 16 bits, for inputs too
-    // small to repay the second launch, and with LDDL_TOKENIZE_PATH=plain.
-    constexpr int64_t kMemoMinSample = 1 << 14;
-    int64_t n_sample = std::max<int64_t>(n_sent / kMemoDiv, kMemoMinSample);
-    bool memo = c->vocab_size <= 65536 && n_sent >= 4 * kMemoMinSample;
-    if (const char* e = getenv("LDDL_TOKENIZE_MEMO_SAMPLE")) {  // tests: the memo on small inputs
-      n_sample = atoll(e);
-      memo = c->vocab_size <= 65536 && n_sample > 0 && n_sample < n_sent;
-    }
-    if (path && !strcmp(path, "plain")) memo = false;
-    int rc = 0;
-    if (!memo) {
-      rc = pass(0, n_sent, kMemoOff, WordMemo{nullptr, 0});
-    } else {
-      DevArena::Block mb;
-      const size_t entries = (size_t)1 << kMemoLog2;
-      LDDL_HIP(c->arena.take(64 * entries, st, mb));
-      LDDL_HIP(hipMemsetAsync(mb.p, 0, 64 * entries, st));
-      const WordMemo M{static_cast<uint4*>(mb.p), (uint32_t)(entries - 1)};
-      rc = pass(0, n_sample, kMemoBuild, M);
-      if (!rc) rc = pass(n_sample, n_sent - n_sample, kMemoLookup, M);
-      c->arena.give(mb, st);
-    }
-    if (rc) {
-      c->arena.give(fbb, st);
+    ArenaTmp mb(&c->arena, st);
+    const size_t entries = (size_t)1 << kMemoLog2;
+    LDDL_HIP(mb.take(64 * entries));
+    LDDL_HIP(hipMemsetAsync(mb.as<void>(), 0, 64 * entries, st));
+    const WordMemo M{mb.as<uint4>(), (uint32_t)(entries - 1)};
+    if ((rc = batch_pass(T, grid_max, 0, n_sample, kMemoBuild, M)) ||
+        (rc = batch_pass(T, grid_max, n_sample, n_sent - n_sample, kMemoLookup, M)))
       return rc;
-    }
+  }
 #ifdef LDDL_STAMPS
-    {  // wave timeline (100 MHz real-time clock)
-      const int64_t nw = grid * wpb;
-      std::vector<unsigned long long> t(2 * nw);
-      LDDL_HIP(hipMemcpyAsync(t.data(), tl, 16 * nw, hipMemcpyDeviceToHost, st));
-      LDDL_HIP(hipStreamSynchronize(st));
-      unsigned long long t0 = ~0ull, t1 = 0;
-      std::vector<double> e(nw);
-      for (int64_t q = 0; q < nw; ++q) {
-        t0 = std::min(t0, t[2 * q]);
-        t1 = std::max(t1, t[2 * q + 1]);
-      }
-      for (int64_t q = 0; q < nw; ++q) e[q] = (t[2 * q + 1] - t0) / 1e5;
-      std::sort(e.begin(), e.end());
-      const double span = (t1 - t0) / 1e5;
-      fprintf(stderr, "[tok timeline] span %.2f ms, wave end ms: min %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f\n",
-              span, e[0], e[nw / 10], e[nw / 2], e[nw * 9 / 10], e[nw - 1]);
-      const int nb = 40;
-      fprintf(stderr, "[tok timeline] waves alive per %.2f ms bin:", span / nb);
-      for (int b = 0; b < nb; ++b) {
-        const double te = span * (b + 0.5) / nb;
-        int64_t alive = 0;
-        for (int64_t q = 0; q < nw; ++q) alive += e[q] > te;
-        fprintf(stderr, " %lld", (long long)alive);
-      }
-      fprintf(stderr, "\n");
-      LDDL_HIP(hipFree(tl));
-      unsigned long long r[kTokRegions + 10];
-      LDDL_HIP(hipMemcpy(r, rg, sizeof r, hipMemcpyDeviceToHost));
-      const unsigned long long* k = r + kTokRegions;
-      fprintf(stderr,
-              "[tok phaseB] flushes %llu units %llu | passes %llu lanes/pass %.1f | piece-steps: wave %llu "
-              "lane %llu (lane util %.2f) | bloom iters: wave %llu lane-useful %llu (util %.2f, per wave "
-              "step %.1f) | probe trips: wave %llu lane %llu (util %.2f)\n",
-              k[8], k[9], k[0], (double)k[1] / (k[0] ? k[0] : 1), k[2], k[3],
-              (double)k[3] / (64.0 * (k[2] ? k[2] : 1)), k[4], k[5], (double)k[5] / (64.0 * (k[4] ? k[4] : 1)),
-              (double)k[4] / (k[2] ? k[2] : 1), k[6], k[7], (double)k[7] / (64.0 * (k[6] ? k[6] : 1)));
-      unsigned long long tot = 0;
-      for (int q = 0; q < kTokRegions; ++q) tot += r[q];
-      static const char* names[kTokRegions] = {"banks", "phaseA", "phaseB", "place", "qshift", "chunk"};
-      fprintf(stderr, "[tok regions] wave-cycle shares:");
-      for (int q = 0; q < kTokRegions; ++q) fprintf(stderr, " %s %.1f%%", names[q], 100.0 * r[q] / (tot ? tot : 1));
-      fprintf(stderr, "\n");
-      LDDL_HIP(hipFree(rg));
-    }
+  if ((rc = report_tok_stamps(T, tl, rg))) return rc;
 #endif
-  }
-  if (path && !strcmp(path, "wave")) {  // the wave kernel's fallback list
-    const int64_t fgrid = std::min<int64_t>((n_sent + kBlock - 1) / kBlock, (int64_t)n_cu * 2);
-    hipLaunchKernelGGL(tokenize_lane_kernel, dim3((unsigned)fgrid), dim3(kBlock), 0, st, c->tab,
-                       d_text, d_sent_off, n_sent, max_pieces, d_ids, d_sent_len, fb + kFbHead,
-                       reinterpret_cast<const uint32_t*>(fb));
-    LDDL_HIP(hipGetLastError());
-  }
-  c->arena.give(fbb, st);
   return 0;
 }

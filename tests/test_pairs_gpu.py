@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from alloc_util import OWN_ARENA, allocated, needs_torch_arena
 from conftest import GOLDEN, VOCAB_UNCASED
 
 pytestmark = pytest.mark.gpu
@@ -45,19 +46,26 @@ def part_doc_off_for(sizes, kept_lines, n_lines):
     return np.asarray([kept_lines[b] if b < len(kept_lines) else n_lines for b in bounds], np.int64)
 
 
-@pytest.mark.parametrize('name', PAIR_CASES)
-def test_pairs_golden_gpu(name, ctx, docs_dev):
-    from lddl_amd.pairs import make_pairs
+def case_inputs(name, docs_dev):
+    """(golden arrays, make_pairs keyword arguments) of one golden case, tensors on the device."""
     g = load('pairs_{}.npz'.format(name))
     dup, seq, masking = g['params'].tolist()
     pdo = part_doc_off_for(g['part_doc_sizes'], docs_dev['kept_lines'], docs_dev['n_lines'])
-    if pdo[-1] < docs_dev['n_lines']:  # docs after the last golden partition are not used
-        pass
-    out = make_pairs(ctx, docs_dev['sent_off'], docs_dev['ids'], docs_dev['sent_len'],
-                     docs_dev['doc_sent_off'], torch.from_numpy(pdo).cuda(),
-                     torch.from_numpy(g['seeds'].astype(np.int64)).cuda(), seq=seq, dup=dup,
-                     masking=bool(masking), short_seq_prob=float(g['short_seq_prob']),
-                     masked_lm_ratio=float(g['ratio'])).to_host()
+    # (docs after the last golden partition are not used)
+    kw = dict(sent_off=docs_dev['sent_off'], ids=docs_dev['ids'], sent_len=docs_dev['sent_len'],
+              doc_sent_off=docs_dev['doc_sent_off'], part_doc_off=torch.from_numpy(pdo).cuda(),
+              part_seed=torch.from_numpy(g['seeds'].astype(np.int64)).cuda(), seq=seq, dup=dup,
+              masking=bool(masking), short_seq_prob=float(g['short_seq_prob']),
+              masked_lm_ratio=float(g['ratio']))
+    return g, kw
+
+
+@pytest.mark.parametrize('name', PAIR_CASES)
+def test_pairs_golden_gpu(name, ctx, docs_dev):
+    from lddl_amd.pairs import make_pairs
+    g, kw = case_inputs(name, docs_dev)
+    masking = kw['masking']
+    out = make_pairs(ctx, **kw).to_host()
     n = len(g['num_tokens'])
     assert len(out['len_a']) == n
     np.testing.assert_array_equal(out['is_random_next'], g['is_random_next'])
@@ -98,14 +106,53 @@ def test_fy_resolve_variants_golden(ctx, docs_dev, monkeypatch, env):
 @pytest.mark.parametrize('env', [{'LDDL_FY_RA': '5'}, {'LDDL_FY_PF': '3'}, {'LDDL_FY_LW': '8'},
                                  {'LDDL_FY_PF': '8', 'LDDL_FY_RA': '2'},
                                  {'LDDL_FY_MODE': '0', 'LDDL_FY_RA': '2'}])
-def test_fy_resolve_rejects_unsupported_knobs(docs_dev, monkeypatch, env):
+def test_fy_resolve_rejects_unsupported_knobs(ctx, docs_dev, monkeypatch, env):
     """Unsupported LDDL_FY_* values and combinations raise instead of falling through to another
-    variant. A fresh Context: the failed call is not allowed to touch the shared one."""
-    from lddl_amd.context import Context
+    variant. On the shared Context: the failed call keeps none of the allocator's
+    memory, and the same context then plans the case with the knobs cleared."""
+    from lddl_amd.pairs import make_pairs
+    _, kw = case_inputs('s512_mask', docs_dev)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
+    before = allocated()
     with pytest.raises(Exception, match='LDDL_FY'):
-        test_pairs_golden_gpu('s512_mask', Context(VOCAB_UNCASED, True), docs_dev)
+        make_pairs(ctx, **kw)
+    if not OWN_ARENA:
+        assert allocated() == before
+    for k in env:
+        monkeypatch.delenv(k)
+    test_pairs_golden_gpu('s512_mask', ctx, docs_dev)
+
+
+@needs_torch_arena
+def test_failed_replay_plan_returns_its_blocks(ctx, docs_dev):
+    """A plan that fails after the compaction took its blocks (the replay planner stops at seq
+    512) gives every block back."""
+    from lddl_amd.pairs import make_pairs
+    _, kw = case_inputs('s512_nomask_short', docs_dev)
+    kw.update(masking=False, seq=600)
+    before = allocated()
+    with pytest.raises(Exception, match='replay planner supports target_seq_length <= 512'):
+        make_pairs(ctx, **kw)
+    assert allocated() == before
+
+
+@needs_torch_arena
+@pytest.mark.parametrize('mode', ['replan', 'native'])
+def test_plan_blocks_balance(ctx, docs_dev, monkeypatch, mode):
+    """After a successful plan + gather (through the re-plan, which returns its pools early, and
+    through the native planner) and the deletion of the batch, the allocator is where it was."""
+    from lddl_amd.pairs import make_pairs
+    _, kw = case_inputs('s128_mask', docs_dev)
+    if mode == 'replan':
+        monkeypatch.setenv('LDDL_AMD_MASK_POOL', '100')
+    else:
+        kw['rng'] = 'native'
+    before = allocated()
+    pb = make_pairs(ctx, **kw)
+    assert pb.tokens.numel() > 0 and allocated() > before
+    del pb
+    assert allocated() == before
 
 
 def test_partition_shuffle_global_path(ctx, docs_dev, monkeypatch):

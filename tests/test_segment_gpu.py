@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from alloc_util import allocated, needs_torch_arena
 from conftest import GOLDEN, VOCAB_UNCASED
 
 pytestmark = pytest.mark.gpu
@@ -143,3 +144,31 @@ def test_segmented_path_end_to_end(ctx):
         nts.append(out['num_tokens'])
     np.testing.assert_array_equal(pb['num_tokens'], np.concatenate(nts))
     np.testing.assert_array_equal(pb['tokens'], np.concatenate(toks))
+
+
+@needs_torch_arena
+def test_segment_blocks_balance(ctx, golden):
+    """The pending segmentation's blocks come from torch's allocator at lddl_segment_count and go
+    back at lddl_segment_fill, whether it fills the outputs or cancels (null outputs)."""
+    import ctypes
+    import torch
+    from lddl_amd import punkt
+    from lddl_amd._native import check, lib
+    from lddl_amd.context import _ptr, _stream
+    punkt.set_params(ctx, None)
+    text = torch.from_numpy(np.ascontiguousarray(golden['text'])).cuda()
+    doc_off = torch.from_numpy(np.ascontiguousarray(golden['doc_off'], np.int64)).cuda()
+    before = allocated()
+    so, ds = punkt.segment(ctx, text, doc_off)
+    exp = so.numel() - 1
+    assert exp >= int(golden['untrained_count'].sum())  # (an empty document still has one span)
+    del so, ds
+    assert allocated() == before
+    n_sent = ctypes.c_int64()
+    check(lib.lddl_segment_count(ctx._h, _stream(), _ptr(text), text.numel(), _ptr(doc_off),
+                                 doc_off.numel() - 1, ctypes.byref(n_sent)))
+    assert n_sent.value == exp and allocated() > before
+    check(lib.lddl_segment_fill(ctx._h, _stream(), None, None))
+    assert allocated() == before
+    so, ds = punkt.segment(ctx, text, doc_off)  # the context segments again after the cancel
+    assert so.numel() - 1 == exp

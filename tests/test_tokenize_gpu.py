@@ -4,6 +4,7 @@ import os
 import numpy as np
 import pytest
 
+from alloc_util import allocated, needs_torch_arena
 from conftest import GOLDEN, VOCAB_CASED, VOCAB_UNCASED
 
 pytestmark = pytest.mark.gpu
@@ -197,3 +198,30 @@ def test_tokenize_word_memo_vs_oracle(ctxs, monkeypatch, case, sample):
                 e, eo = tok.tokenize(text, off, max_pieces=mp)
                 _assert_same(ids, o, e, eo, text, off)
             monkeypatch.delenv('LDDL_TOKENIZE_GRID', raising=False)
+
+
+@needs_torch_arena
+def test_tokenize_blocks_balance(ctxs, monkeypatch):
+    """With the word memo forced on, a call takes the fallback list and the 256 MiB memo block
+    from torch's allocator and gives both back: the allocator is where it was once the outputs
+    are deleted, and the outputs are those of the call without the memo."""
+    import torch
+    ctx = ctxs['uncased']
+    g = load('documents_uncased.npz')
+    text = torch.from_numpy(g['text'].copy()).cuda()
+    sent_off = torch.from_numpy(g['sent_off']).cuda()
+    assert sent_off.numel() - 1 > 64
+    ids0, len0 = ctx.tokenize(text, sent_off)
+    monkeypatch.setenv('LDDL_TOKENIZE_MEMO_SAMPLE', '64')
+    before = allocated()
+    torch.cuda.reset_peak_memory_stats()
+    ids, sent_len = ctx.tokenize(text, sent_off)
+    assert torch.equal(sent_len, len0)
+    # every piece of every sentence (the ids between the sentences' pieces are not written)
+    n = (len0 & ((1 << 30) - 1)).long()
+    first = torch.cumsum(n, 0) - n
+    at = torch.repeat_interleave(sent_off[:-1] - first, n) + torch.arange(int(n.sum()), device=n.device)
+    assert torch.equal(ids[at], ids0[at])
+    assert torch.cuda.max_memory_allocated() - before >= 256 << 20  # the memo block was taken
+    del ids, sent_len, n, first, at
+    assert allocated() == before
