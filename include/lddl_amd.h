@@ -171,6 +171,31 @@ int lddl_segment_count(lddl_ctx* ctx, void* stream, const uint8_t* d_text, int64
 int lddl_segment_fill(lddl_ctx* ctx, void* stream, int64_t* d_sent_off, int64_t* d_doc_sent_off);
 
 /* ---------------------------------------------------------------------------------------------
+ * BART pretraining chunks (device in, device out).
+ * Replaces `_aggregate_sentences` (lddl/dask/bart/pretrain.py:88-128) for every document of a
+ * batch, over the layout lddl_segment_fill writes: per document, in sentence order,
+ *   chunk += " " + sentence.strip(); num_tokens += len(sentence.split());
+ *   emit and reset when num_tokens >= target_words; emit the remainder if num_tokens > 0.
+ * Whitespace is str.isspace() (the class table of lddl_punkt_set_params, which must have been
+ * called); a whitespace-only sentence is skipped. target_words is the reference's
+ * target_seq_length - 3 (<= 0: every non-empty sentence is its own chunk).
+ * lddl_bart_count: d_sent_off[n_sent+1] (monotone, inside [0, n_bytes], sentences < 2 GiB, cut at
+ *   code point boundaries of valid UTF-8), d_doc_sent_off[n_doc+1] (monotone, from 0 to n_sent).
+ *   Returns the number of chunks and the bytes of all chunk strings (synchronises the stream).
+ *   Exactly one lddl_bart_fill must follow on the same ctx; d_text and both offset arrays must
+ *   stay valid until then.
+ * lddl_bart_fill -> d_out[n_out_bytes]: the chunk strings back to back (each starts with one
+ *   space), d_chunk_off[n_chunks+1] their byte offsets, d_num_tokens[n_chunks] their word counts
+ *   (may be NULL), d_doc_chunk_off[n_doc+1] the chunk offsets of the documents. All four NULL
+ *   cancels the pending aggregation (releases its scratch).
+ * ------------------------------------------------------------------------------------------- */
+int lddl_bart_count(lddl_ctx* ctx, void* stream, const uint8_t* d_text, int64_t n_bytes,
+                    const int64_t* d_sent_off, int64_t n_sent, const int64_t* d_doc_sent_off,
+                    int64_t n_doc, int32_t target_words, int64_t* n_chunks, int64_t* n_out_bytes);
+int lddl_bart_fill(lddl_ctx* ctx, void* stream, uint8_t* d_out, int64_t* d_chunk_off,
+                   int32_t* d_num_tokens, int64_t* d_doc_chunk_off);
+
+/* ---------------------------------------------------------------------------------------------
  * NSP pairs + static masking for a batch of partitions (device in, device out).
  * Replaces `_to_partition_pairs` (lddl/dask/bert/pretrain.py:386-402) =
  *   for dup in range(duplicate_factor): for doc: create_pairs_from_document(...)  (241-365)

@@ -45,6 +45,9 @@ SIGNATURES = {
     'lddl_segment_count': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64,
                                           ctypes.POINTER(c_i64)]),
     'lddl_segment_fill': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    'lddl_bart_count': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32,
+                                       ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    'lddl_bart_fill': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'lddl_tokenize': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp]),
     'lddl_pairs_plan': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
                                        c_vp, c_i64, ctypes.POINTER(c_vp), c_vp]),

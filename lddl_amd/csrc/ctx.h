@@ -31,8 +31,12 @@ struct lddl_ctx {
   std::vector<std::string> tokens;  // host copy of the vocab lines
   lddl::DevArena arena;             // per-call temporaries (pair plans)
   void* punkt = nullptr;            // lddl_punkt_state (segment.hip), created by lddl_punkt_set_params
+  void* bart = nullptr;             // lddl_bart_state (bart.hip), created by lddl_bart_count
 };
 extern "C" void lddl_punkt_release(lddl_ctx* c);
+extern "C" void lddl_bart_release(lddl_ctx* c);
+// the character class table of lddl_punkt_set_params (bit 0 = str.isspace()); 0 if it was never set
+extern "C" int lddl_punkt_tables(lddl_ctx* c, const uint16_t** l1, const uint8_t** pages);
 
 namespace lddl {
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

@@ -194,6 +194,7 @@ extern "C" int lddl_ctx_create(int device, const uint8_t* norm_table, int64_t ta
 extern "C" int lddl_ctx_destroy(lddl_ctx* c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
+  lddl_bart_release(c);
   lddl_punkt_release(c);
   for (void* p : {(void*)c->d_l1, (void*)c->d_pages, (void*)c->d_pool, (void*)c->d_vhash,
                   (void*)c->d_vbytes, (void*)c->d_voff, (void*)c->d_render, (void*)c->d_render_off,

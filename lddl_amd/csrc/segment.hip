@@ -709,6 +709,14 @@ static lddl_punkt_state* punkt_of(lddl_ctx* c) {
   return reinterpret_cast<lddl_punkt_state*>(c->punkt);
 }
 
+extern "C" int lddl_punkt_tables(lddl_ctx* c, const uint16_t** l1, const uint8_t** pages) {
+  lddl_punkt_state* p = punkt_of(c);
+  if (!p || !p->l1) return 0;
+  *l1 = p->l1;
+  *pages = p->pages;
+  return 1;
+}
+
 extern "C" void lddl_punkt_release(lddl_ctx* c) {
   lddl_punkt_state* p = punkt_of(c);
   if (!p) return;

@@ -13,6 +13,7 @@ setup(
     entry_points={
         'console_scripts': [
             'preprocess_bert_pretrain=lddl_amd.dask.bert.pretrain:console_script',
+            'preprocess_bart_pretrain=lddl_amd.dask.bart.pretrain:console_script',
             'balance_dask_output=lddl_amd.dask.load_balance:console_script',
             'generate_num_samples_cache=lddl_amd.dask.load_balance:generate_num_samples_cache',
         ],
