@@ -341,6 +341,21 @@ int lddl_collate_encode(lddl_ctx* ctx, void* stream, const uint8_t* d_bytes, con
                         const int64_t* d_lab_off, const uint16_t* d_pos, const int64_t* d_pos_off,
                         int64_t* d_labels, int64_t ignore_index);
 
+/* The static-masking collate of the model-parallel loader (lddl/torch_mp/bert.py:69-153): as
+ * lddl_collate_encode, plus d_loss_mask int64 [batch, seq_len] = 1 at the sample's
+ * masked_lm_positions (duplicates included, whatever the labels string holds), else 0; written
+ * by the same kernel in the same pass. Fails with -1 before anything is launched if d_loss_mask,
+ * d_labels or a static-masking input (d_lab_bytes, d_lab_off, d_pos, d_pos_off) is NULL. The
+ * other outputs are bit-identical to lddl_collate_encode's. */
+int lddl_collate_encode_mp(lddl_ctx* ctx, void* stream, const uint8_t* d_bytes,
+                           const int64_t* d_a_off, const int64_t* d_b_off, const int32_t* d_na,
+                           const int32_t* d_nb, int32_t batch, int32_t seq_len,
+                           int64_t* d_input_ids, int64_t* d_token_type_ids,
+                           int64_t* d_attention_mask, int64_t* d_special_tokens_mask,
+                           const uint8_t* d_lab_bytes, const int64_t* d_lab_off,
+                           const uint16_t* d_pos, const int64_t* d_pos_off, int64_t* d_labels,
+                           int64_t ignore_index, int64_t* d_loss_mask);
+
 /* The loader's dynamic-masking collate in one pass (lddl/torch/bert.py:348-365 =
  * _to_encoded_inputs + _mask_tokens): as lddl_collate_encode (dynamic), then the native-RNG
  * masking of lddl_mask_dynamic applied to each slot as it is written; outputs input_ids (masked),

@@ -75,6 +75,9 @@ SIGNATURES = {
     'lddl_collate_encode': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_i64]),
+    'lddl_collate_encode_mp': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                              c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_i64, c_vp]),
     'lddl_utf8_check': (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     'lddl_collate_encode_masked': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
                                                   c_i32, c_vp, c_vp, c_vp, c_vp, ctypes.c_float,

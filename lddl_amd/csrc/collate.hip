@@ -5,6 +5,9 @@
 //                         fill input_ids / token_type_ids / attention_mask and either
 //                         special_tokens_mask (dynamic) or labels from masked_lm_positions /
 //                         masked_lm_labels (static). One wave per sample.
+//   lddl_collate_encode_mp   the same with static masking plus the [B, L] loss mask of
+//                         lddl/torch_mp/bert.py:103-105 (1 at masked_lm_positions), written in
+//                         the same output loop.
 //   lddl_mask_dynamic     _mask_tokens (bert.py:152-196): per slot masked ~ Bernoulli(p) unless
 //                         special; of the masked, Bernoulli(0.8) -> [MASK], else Bernoulli(0.5) ->
 //                         random id in [0, len(tokenizer)), else unchanged; labels = id where
@@ -125,6 +128,7 @@ struct EncodeArgs {
   const uint16_t* pos;
   const int64_t* pos_off;
   int64_t* labels;
+  int64_t* loss_mask;  // static masking (nullable): 1 at the sample's masked_lm_positions, else 0
   int64_t ignore_index;
   int32_t fused_mask;  // 1: dynamic masking applied on the way out (labels written from it)
   MaskDraw draw;
@@ -158,8 +162,18 @@ __global__ void __launch_bounds__(64 * kEncWaves) encode_kernel(EncodeArgs E) {
     split_lookup(E.T, E.bytes, E.b_off[b], E.b_off[b + 1], sid + na + 2, nb, nullptr, E.L);
     if (E.labels && E.lab_bytes) {  // labels[b, positions] = ids of masked_lm_labels (bert.py:120-125)
       const int64_t p0 = E.pos_off[b];
-      split_lookup(E.T, E.lab_bytes, E.lab_off[b], E.lab_off[b + 1], slab,
-                   (int32_t)(E.pos_off[b + 1] - p0), E.pos + p0, E.L);
+      const int32_t npos = (int32_t)(E.pos_off[b + 1] - p0);
+      if (E.loss_mask) {
+        // the loss mask follows the positions, not "a label was found": mark them -2 in the
+        // labels row (still < 0 = ignore_index if the labels string is short). The label ids
+        // land on the same LDS words from other lanes of this wave: marks first.
+        for (int32_t k = lane; k < npos; k += 64) {
+          const int32_t p = E.pos[p0 + k];
+          if (p < E.L) slab[p] = -2;
+        }
+        wave_sync();
+      }
+      split_lookup(E.T, E.lab_bytes, E.lab_off[b], E.lab_off[b + 1], slab, npos, E.pos + p0, E.L);
     }
   }
   __syncthreads();
@@ -174,6 +188,7 @@ __global__ void __launch_bounds__(64 * kEncWaves) encode_kernel(EncodeArgs E) {
     } else {
       E.input_ids[row + x] = sid[x];
       if (E.labels) E.labels[row + x] = slab[x] < 0 ? E.ignore_index : (int64_t)slab[x];
+      if (E.loss_mask) E.loss_mask[row + x] = slab[x] != -1 ? 1 : 0;
     }
     E.token_type_ids[row + x] = (x >= na + 2 && x < end) ? 1 : 0;
     E.attention_mask[row + x] = x < end ? 1 : 0;
@@ -239,6 +254,28 @@ __global__ void __launch_bounds__(256) mask_kernel(MaskArgs M) {
 
 using namespace lddl;
 
+// lddl_collate_encode (d_loss_mask == nullptr) and lddl_collate_encode_mp
+static int collate_encode(lddl_ctx* c, void* stream, const uint8_t* d_bytes, const int64_t* d_a_off,
+                          const int64_t* d_b_off, const int32_t* d_na, const int32_t* d_nb,
+                          int32_t batch, int32_t seq_len, int64_t* d_input_ids,
+                          int64_t* d_token_type_ids, int64_t* d_attention_mask,
+                          int64_t* d_special_tokens_mask, const uint8_t* d_lab_bytes,
+                          const int64_t* d_lab_off, const uint16_t* d_pos, const int64_t* d_pos_off,
+                          int64_t* d_labels, int64_t* d_loss_mask, int64_t ignore_index) {
+  if (batch <= 0 || seq_len <= 0) return 0;
+  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0)
+    LDDL_FAIL(-1, "vocab needs [CLS] and [SEP]");
+  EncodeArgs E{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len, d_input_ids,
+               d_token_type_ids, d_attention_mask, d_special_tokens_mask, d_lab_bytes, d_lab_off,
+               d_pos, d_pos_off, d_labels, d_loss_mask, ignore_index, 0, {}};
+  const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;
+  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", seq_len);
+  hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
+                     dim3(64 * kEncWaves), lds, as_stream(stream), E);
+  LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" int lddl_collate_encode(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
                                    const int64_t* d_a_off, const int64_t* d_b_off,
                                    const int32_t* d_na, const int32_t* d_nb, int32_t batch,
@@ -248,18 +285,28 @@ extern "C" int lddl_collate_encode(lddl_ctx* c, void* stream, const uint8_t* d_b
                                    const uint16_t* d_pos, const int64_t* d_pos_off,
                                    int64_t* d_labels, int64_t ignore_index) {
   if (!c) LDDL_FAIL(-1, "null ctx");
-  if (batch <= 0 || seq_len <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS] and [SEP]");
-  EncodeArgs E{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len, d_input_ids,
-               d_token_type_ids, d_attention_mask, d_special_tokens_mask, d_lab_bytes, d_lab_off,
-               d_pos, d_pos_off, d_labels, ignore_index, 0, {}};
-  const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;
-  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", seq_len);
-  hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
-                     dim3(64 * kEncWaves), lds, as_stream(stream), E);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  return collate_encode(c, stream, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len,
+                        d_input_ids, d_token_type_ids, d_attention_mask, d_special_tokens_mask,
+                        d_lab_bytes, d_lab_off, d_pos, d_pos_off, d_labels, nullptr, ignore_index);
+}
+
+extern "C" int lddl_collate_encode_mp(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
+                                      const int64_t* d_a_off, const int64_t* d_b_off,
+                                      const int32_t* d_na, const int32_t* d_nb, int32_t batch,
+                                      int32_t seq_len, int64_t* d_input_ids,
+                                      int64_t* d_token_type_ids, int64_t* d_attention_mask,
+                                      int64_t* d_special_tokens_mask, const uint8_t* d_lab_bytes,
+                                      const int64_t* d_lab_off, const uint16_t* d_pos,
+                                      const int64_t* d_pos_off, int64_t* d_labels,
+                                      int64_t ignore_index, int64_t* d_loss_mask) {
+  if (!c) LDDL_FAIL(-1, "null ctx");
+  if (!d_loss_mask) LDDL_FAIL(-1, "null loss mask");
+  if (!d_lab_bytes || !d_lab_off || !d_pos || !d_pos_off || !d_labels)
+    LDDL_FAIL(-1, "the loss mask needs the static-masking inputs and labels");
+  return collate_encode(c, stream, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len,
+                        d_input_ids, d_token_type_ids, d_attention_mask, d_special_tokens_mask,
+                        d_lab_bytes, d_lab_off, d_pos, d_pos_off, d_labels, d_loss_mask,
+                        ignore_index);
 }
 
 extern "C" int lddl_mask_dynamic(lddl_ctx* c, void* stream, int64_t* d_input_ids, int64_t* d_labels,
@@ -300,7 +347,7 @@ extern "C" int lddl_collate_encode_masked(lddl_ctx* c, void* stream, const uint8
     LDDL_FAIL(-1, "null output");
   EncodeArgs E{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len, d_input_ids,
                d_token_type_ids, d_attention_mask, nullptr, nullptr, nullptr, nullptr, nullptr,
-               d_labels, ignore_index, 1,
+               d_labels, nullptr, ignore_index, 1,
                MaskDraw{mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, seed,
                         counter}};
   const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;

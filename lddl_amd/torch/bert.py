@@ -135,8 +135,12 @@ def _mask_tokens(inputs, special_tokens_mask=None, tokenizer=None, mlm_probabili
 
 
 def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=None, events=None,
-                  stager=None):
+                  stager=None, loss_mask=False):
     """`_to_encoded_inputs` on an already packed batch (main process, GPU).
+
+    loss_mask=True is lddl.torch_mp's `_to_encoded_inputs`: a static-masking batch also gets
+    `masked_lm_positions`, the [B, L] loss mask (lddl_collate_encode_mp, same kernel and pass);
+    a dynamic-masking batch is unchanged, as in the reference.
 
     mask = (mlm_probability, seed, counter) on a dynamic-masking batch runs `_mask_tokens` fused
     into the same kernel (lddl_collate_encode_masked) and returns `labels` instead of
@@ -180,18 +184,26 @@ def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=No
         labels = torch.empty(B, L, dtype=torch.long, device=dev)
     else:
         stm = torch.empty(B, L, dtype=torch.long, device=dev)
+    args = (ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b), _ptr(d_na), _ptr(d_nb), B, L,
+            _ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']),
+            _ptr(stm), _ptr(d_blob) if pk.static else None, _ptr(d_lab_off), _ptr(d_pos),
+            _ptr(d_pos_off), _ptr(labels), ignore_index)
+    lm = None
+    if loss_mask and pk.static:
+        lm = torch.empty(B, L, dtype=torch.long, device=dev)
     if events is not None:
         events[0].record()
-    check(lib.lddl_collate_encode(ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b),
-                                  _ptr(d_na), _ptr(d_nb), B, L, _ptr(out['input_ids']),
-                                  _ptr(out['token_type_ids']), _ptr(out['attention_mask']),
-                                  _ptr(stm), _ptr(d_blob) if pk.static else None, _ptr(d_lab_off),
-                                  _ptr(d_pos), _ptr(d_pos_off), _ptr(labels), ignore_index))
+    if lm is not None:
+        check(lib.lddl_collate_encode_mp(*args, _ptr(lm)))
+    else:
+        check(lib.lddl_collate_encode(*args))
     if events is not None:
         events[1].record()
     out['next_sentence_labels'] = d_nsl
     if pk.static:
         out['labels'] = labels
+        if lm is not None:
+            out['masked_lm_positions'] = lm
     else:
         out['special_tokens_mask'] = stm
     return out
@@ -216,8 +228,11 @@ class GPUCollateLoader:
     """Iterates a torch DataLoader of PackedBatch and finishes the collate on the GPU."""
 
     def __init__(self, loader, ctx, mlm_probability, ignore_index, sequence_length_alignment,
-                 extra_collate, seed, start_epoch=0, stager=None):
+                 extra_collate, seed, start_epoch=0, stager=None, loss_mask=False):
         self._loader = loader
+        # lddl.torch_mp: static batches carry masked_lm_positions (lddl.torch calls encode_packed
+        # exactly as before)
+        self._mp = {'loss_mask': True} if loss_mask else {}
         self._lazy = ctx if isinstance(ctx, _LazyContext) else None
         self._ctx_obj = None if self._lazy is not None else ctx
         self._mlm = mlm_probability
@@ -265,7 +280,7 @@ class GPUCollateLoader:
             with torch.no_grad():  # dynamic masking: collate + _mask_tokens in one kernel
                 enc = encode_packed(pk, ctx, self._align, self._ignore,
                                     mask=(self._mlm, self._seed, self._counter), events=ev,
-                                    stager=self._stager)
+                                    stager=self._stager, **self._mp)
             if not pk.static:
                 self._counter += 1
             if self.stats is not None:
@@ -276,7 +291,8 @@ class GPUCollateLoader:
 
 def mask_seed(base_seed, rank, bin_id=-1):
     """64-bit Philox key of one (rank, bin) loader's dynamic masking: independent streams per
-    rank and per bin (the reference draws all of them from each worker's torch RNG)."""
+    rank and per bin (the reference draws all of them from each worker's torch RNG). The
+    model-parallel loader passes its dp_rank: one stream per data-parallel group and bin."""
     return ((int(base_seed) * 1000003 + int(rank)) * 65537 + int(bin_id) + 1) & ((1 << 64) - 1)
 
 
@@ -299,8 +315,24 @@ def get_bert_pretrain_data_loader(path, local_rank=0, shuffle_buffer_size=16384,
     tokenizer_class is accepted for compatibility (BertTokenizerFast / BertTokenizer or None):
     the vocab file is loaded into a lddl_amd Context (vocab hash in HBM). vocab_file must be a
     local path (no model-name download offline)."""
+    return _bert_pretrain_data_loader(
+        path, local_rank, None, shuffle_buffer_size, shuffle_buffer_warmup_factor,
+        tokenizer_class, vocab_file, tokenizer_kwargs, data_loader_class, data_loader_kwargs,
+        mlm_probability, base_seed, log_dir, log_level, return_raw_samples, start_epoch,
+        sequence_length_alignment, ignore_index)
+
+
+def _bert_pretrain_data_loader(path, local_rank, dp_rank, shuffle_buffer_size,
+                               shuffle_buffer_warmup_factor, tokenizer_class, vocab_file,
+                               tokenizer_kwargs, data_loader_class, data_loader_kwargs,
+                               mlm_probability, base_seed, log_dir, log_level, return_raw_samples,
+                               start_epoch, sequence_length_alignment, ignore_index):
+    """The loader of lddl.torch (dp_rank None) and of lddl.torch_mp (dp_rank given: files are
+    strided and workers seeded by data-parallel rank, static batches carry the loss mask, and the
+    dynamic-masking key is the group's, so all ranks of a group yield the same batches)."""
     assert isinstance(path, str)
     assert isinstance(local_rank, int) and local_rank >= 0
+    assert dp_rank is None or (isinstance(dp_rank, int) and dp_rank >= 0)
     assert isinstance(shuffle_buffer_size, int) and shuffle_buffer_size > 0
     assert isinstance(shuffle_buffer_warmup_factor, int) and shuffle_buffer_warmup_factor > 0
     if tokenizer_class is not None:
@@ -325,7 +357,8 @@ def get_bert_pretrain_data_loader(path, local_rank=0, shuffle_buffer_size=16384,
                            local_rank=local_rank, log_level=log_level)
     dataset_kwargs = dict(local_rank=local_rank, shuffle_buffer_size=shuffle_buffer_size,
                           shuffle_buffer_warmup_factor=shuffle_buffer_warmup_factor,
-                          base_seed=base_seed, logger=logger, start_epoch=start_epoch)
+                          base_seed=base_seed, logger=logger, start_epoch=start_epoch,
+                          dp_rank=dp_rank)
     extra_collate = data_loader_kwargs.get('collate_fn', lambda x: x)
     ctx = stager = None
     if not return_raw_samples:  # the Context is created after the workers start (_LazyContext)
@@ -333,6 +366,7 @@ def get_bert_pretrain_data_loader(path, local_rank=0, shuffle_buffer_size=16384,
         stager = HostStager()
         data_loader_kwargs['collate_fn'] = _pack_batch
     data_loader_kwargs['persistent_workers'] = True
+    mask_rank = get_rank() if dp_rank is None else dp_rank
 
     def make(paths, bin_id=-1):
         dl = data_loader_class(BertPretrainDataset(paths, **dataset_kwargs), **data_loader_kwargs)
@@ -340,7 +374,8 @@ def get_bert_pretrain_data_loader(path, local_rank=0, shuffle_buffer_size=16384,
             return dl
         return GPUCollateLoader(dl, ctx, mlm_probability, ignore_index,
                                 sequence_length_alignment, extra_collate,
-                                mask_seed(base_seed, get_rank(), bin_id), start_epoch, stager)
+                                mask_seed(base_seed, mask_rank, bin_id), start_epoch, stager,
+                                loss_mask=dp_rank is not None)
 
     paths = get_all_parquets_under(path)
     bin_ids = get_all_bin_ids(paths)

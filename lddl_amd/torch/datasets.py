@@ -6,7 +6,9 @@
   base_seed + epoch), then `files[rank::world][worker::num_workers]` (247-272);
 * a shuffle buffer per worker (46-109): once warm, each incoming sample replaces a random slot
   (`randrange` on a state seeded with base_seed + (epoch * world + rank) * workers + worker) whose
-  old occupant is yielded; the tail is shuffled.
+  old occupant is yielded; the tail is shuffled;
+* with a `dp_rank` (lddl/torch_mp/datasets.py), `files[dp_rank::groups]` and `dp_rank` in the
+  seed instead: the ranks of one data-parallel group yield the same samples.
 Every rank yields num_samples_per_file * files_per_rank samples (files hold N or N+1 samples
 after load balancing; the +1 is dropped). The reference asserts min + 1 == max and so fails on
 perfectly balanced shards; this build accepts max - min <= 1.
@@ -21,7 +23,8 @@ from torch.utils.data import IterableDataset, get_worker_info
 from ..random import randrange, sample, seeded_state, shuffle
 from ..types import File
 from ..utils import get_num_samples_of_parquet
-from .utils import get_nproc_per_node, get_num_nodes, get_node_rank, get_rank, get_world_size
+from .utils import (get_dp_size, get_nproc_per_node, get_num_nodes, get_node_rank, get_rank,
+                    get_world_size)
 
 
 class ShuffleBuffer:
@@ -79,7 +82,8 @@ def _identity(x):
 
 class ParquetDataset(IterableDataset):
     def __init__(self, file_paths, transform=_identity, local_rank=0, shuffle_buffer_size=16384,
-                 shuffle_buffer_warmup_factor=16, base_seed=12345, logger=None, start_epoch=0):
+                 shuffle_buffer_warmup_factor=16, base_seed=12345, logger=None, start_epoch=0,
+                 dp_rank=None):
         super().__init__()
         self._transform = transform
         self._local_rank = local_rank
@@ -91,6 +95,12 @@ class ParquetDataset(IterableDataset):
         self._nproc_per_node = get_nproc_per_node(local_rank)
         self._num_nodes = get_num_nodes(nproc_per_node=self._nproc_per_node)
         self._node_rank = get_node_rank(nproc_per_node=self._nproc_per_node)
+        # who shares samples: every rank reads its own (lddl.torch), or the ranks of one
+        # data-parallel group read the same (lddl.torch_mp)
+        if dp_rank is None:
+            self._group, self._num_groups = self._rank, self._world_size
+        else:  # _num_dp_groups of lddl/torch_mp/datasets.py:137
+            self._group, self._num_groups = dp_rank, get_dp_size(dp_rank)
         self._epoch = start_epoch - 1
         self._logger = logger
         assert len(file_paths) % self._num_nodes == 0
@@ -132,7 +142,7 @@ class ParquetDataset(IterableDataset):
         return [File(fp, n) for fp, n in zip(file_paths, counts.tolist())]
 
     def __len__(self):
-        return self._num_samples_per_file * len(self._files) // self._world_size
+        return self._num_samples_per_file * len(self._files) // self._num_groups
 
     @property
     def num_samples_per_file(self):
@@ -140,7 +150,7 @@ class ParquetDataset(IterableDataset):
 
     @property
     def num_files_per_rank(self):
-        return len(self._files) // self._world_size
+        return len(self._files) // self._num_groups
 
     def _decode_record_batch(self, b):
         raise NotImplementedError('ParquetDataset is an abstract/interface class!')
@@ -154,8 +164,9 @@ class ParquetDataset(IterableDataset):
 
     def _init_rng_states(self, worker_rank, num_workers):
         self._world_rng_state = seeded_state(self._base_seed + self._epoch)
+        # the multiplier is the world size with a dp_rank too (lddl/torch_mp/datasets.py:257-260)
         self._worker_rng_state = seeded_state(
-            self._base_seed + (self._epoch * self._world_size + self._rank) * num_workers +
+            self._base_seed + (self._epoch * self._world_size + self._group) * num_workers +
             worker_rank)
 
     def __iter__(self):
@@ -165,7 +176,7 @@ class ParquetDataset(IterableDataset):
         files, self._world_rng_state = sample(self._files, len(self._files),
                                               rng_state=self._world_rng_state)
         self._logger.to('node').warning('epoch = {}'.format(self._epoch))
-        worker_files = files[self._rank::self._world_size][wr::nw]
+        worker_files = files[self._group::self._num_groups][wr::nw]
         sb = ShuffleBuffer(worker_files, self._num_samples_per_file * len(worker_files),
                            self._decode_record_batch, self._shuffle_buffer_size,
                            self._shuffle_buffer_warmup_factor, self._logger,

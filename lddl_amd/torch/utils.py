@@ -1,4 +1,4 @@
-"""Rank / node helpers (lddl/torch/utils.py:28-94)."""
+"""Rank / node helpers (lddl/torch/utils.py:28-94, lddl/torch_mp/utils.py:33-51)."""
 import torch
 
 
@@ -25,6 +25,17 @@ def get_nproc_per_node(local_rank):
         return 1
     dev = 'cuda' if torch.distributed.get_backend() == 'nccl' else 'cpu'
     t = torch.tensor(local_rank, device=dev)
+    torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+    return int(t.item()) + 1
+
+
+def get_dp_size(dp_rank):
+    """Number of data-parallel groups (lddl/torch_mp/utils.py:33-51): max(dp_rank) + 1 over the
+    world (all_reduce MAX, on the GPU under RCCL); 1 without a process group."""
+    if not _dist_on():
+        return 1
+    dev = 'cuda' if torch.distributed.get_backend() == 'nccl' else 'cpu'
+    t = torch.tensor(dp_rank, device=dev)
     torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     return int(t.item()) + 1
 
