@@ -387,6 +387,36 @@ int lddl_mask_dynamic(lddl_ctx* ctx, void* stream, int64_t* d_input_ids, int64_t
                       const uint8_t* d_r_masked, const uint8_t* d_r_replaced,
                       const uint8_t* d_r_random, const int64_t* d_r_words);
 
+/* ---------------------------------------------------------------------------------------------
+ * Whole-word dynamic masking (Google BERT's do_whole_word_mask; past the reference). A slot is a
+ * continuation iff it is not special, is not the row's first slot, the slot before it is not
+ * special, and its id is a continuation id: 0 <= id < vocab size of the context and the vocab
+ * line starts with "##" and is longer than 2 bytes (decided from the id, never from a string).
+ * head(x) = the largest h <= x that is not a continuation. With r(i) the Philox output that
+ * lddl_mask_dynamic draws for flat slot i (same seed / counter):
+ *   masked(x) = !special(x) && u01(r(head(x)).x) < mlm_probability;
+ * 80 / 10 / 10 and the random id come from the slot's own r(x).y/.z/.w, labels as before. A row
+ * without continuation ids comes out bit-identical to the plain entry point's.
+ *
+ * lddl_mask_dynamic_ww: lddl_mask_dynamic's native mode (no replay). One wave per row.
+ * lddl_collate_encode_masked_ww: lddl_collate_encode_masked with the whole-word decision;
+ * bit-identical to lddl_collate_encode followed by lddl_mask_dynamic_ww.
+ * Both fail with -1 on a NULL context or a vocab without [MASK].
+ * ------------------------------------------------------------------------------------------- */
+int lddl_mask_dynamic_ww(lddl_ctx* ctx, void* stream, int64_t* d_input_ids, int64_t* d_labels,
+                         const int64_t* d_special_tokens_mask, const int32_t* d_na,
+                         const int32_t* d_nb, int64_t batch, int64_t seq_len,
+                         float mlm_probability, int64_t ignore_index, int64_t vocab_len,
+                         uint64_t seed, uint64_t counter);
+
+int lddl_collate_encode_masked_ww(lddl_ctx* ctx, void* stream, const uint8_t* d_bytes,
+                                  const int64_t* d_a_off, const int64_t* d_b_off,
+                                  const int32_t* d_na, const int32_t* d_nb, int32_t batch,
+                                  int32_t seq_len, int64_t* d_input_ids, int64_t* d_token_type_ids,
+                                  int64_t* d_attention_mask, int64_t* d_labels,
+                                  float mlm_probability, int64_t ignore_index, int64_t vocab_len,
+                                  uint64_t seed, uint64_t counter);
+
 #ifdef __cplusplus
 }
 #endif

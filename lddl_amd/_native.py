@@ -85,6 +85,11 @@ SIGNATURES = {
     'lddl_mask_dynamic': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                          ctypes.c_float, c_i64, c_i64, c_u64, c_u64, c_vp, c_vp,
                                          c_vp, c_vp]),
+    'lddl_mask_dynamic_ww': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                            ctypes.c_float, c_i64, c_i64, c_u64, c_u64]),
+    'lddl_collate_encode_masked_ww': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                     c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                     ctypes.c_float, c_i64, c_i64, c_u64, c_u64]),
 }
 
 

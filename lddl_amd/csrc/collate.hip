@@ -20,10 +20,17 @@
 //                         labels are each written once (36 B per slot incl. the string read)
 //                         and no special_tokens_mask is materialised; bit-identical to
 //                         lddl_collate_encode followed by lddl_mask_dynamic (same Philox stream).
+//   lddl_mask_dynamic_ww / lddl_collate_encode_masked_ww   the same two with whole-word masking
+//                         (DESIGN §15): a word = a head plus the continuation ("##x") ids behind
+//                         it, and the word's masked / not masked decision is its head's draw. One
+//                         wave per row, heads found by ballot; kernels of their own, the plain
+//                         ones are untouched.
 #include "common.h"
 #include "ctx.h"
 #include "device.h"
 #include "lddl_amd.h"
+
+#include <type_traits>
 
 namespace lddl {
 namespace {
@@ -96,18 +103,49 @@ struct MaskDraw {
   int64_t ignore_index, mask_id, vocab_len;
   uint64_t seed, counter;
 };
-__device__ inline int64_t mask_slot(const MaskDraw& D, int64_t flat, bool special, int64_t id,
-                                    int64_t* label) {
-  const uint4 r = Philox::gen(make_uint4((uint32_t)flat, (uint32_t)(flat >> 32), (uint32_t)D.counter,
-                                         (uint32_t)(D.counter >> 32)),
-                              make_uint2((uint32_t)D.seed, (uint32_t)(D.seed >> 32)));
-  const bool masked = !special && u01(r.x) < D.p;
+__device__ inline uint4 mask_draw(const MaskDraw& D, int64_t flat) {
+  return Philox::gen(make_uint4((uint32_t)flat, (uint32_t)(flat >> 32), (uint32_t)D.counter,
+                                (uint32_t)(D.counter >> 32)),
+                     make_uint2((uint32_t)D.seed, (uint32_t)(D.seed >> 32)));
+}
+// the slot's outcome once `masked` is decided: 80 / 10 / 10 and the random id from its own draw
+__device__ inline int64_t mask_apply(const MaskDraw& D, const uint4 r, bool masked, int64_t id,
+                                     int64_t* label) {
   const bool replaced = masked && u01(r.y) < 0.8f;
   const bool rnd = masked && !replaced && u01(r.z) < 0.5f;
   *label = masked ? id : D.ignore_index;
   if (replaced) return D.mask_id;
   if (rnd) return (int64_t)(((uint64_t)r.w * (uint64_t)D.vocab_len) >> 32);
   return id;
+}
+__device__ inline int64_t mask_slot(const MaskDraw& D, int64_t flat, bool special, int64_t id,
+                                    int64_t* label) {
+  const uint4 r = mask_draw(D, flat);
+  return mask_apply(D, r, !special && u01(r.x) < D.p, id, label);
+}
+
+// Whole-word masking. A slot is a continuation iff it and the slot before it are
+// not special and its id is a "##x" vocab entry (the context's per-id bitmap: ids, not strings,
+// so an unknown "##zzz" that became [UNK] is a head). A word's decision is its head's draw.
+struct ContBits {
+  const uint32_t* bits;  // bit id of word id >> 5
+  int32_t vocab_size;
+};
+__device__ inline bool cont_id(const ContBits& C, int64_t id) {
+  return id >= 0 && id < C.vocab_size && ((C.bits[id >> 5] >> (id & 31)) & 1u);
+}
+// One 64-slot window of a row, lane = slot, EVERY lane of the wave calls it (two ballots; lanes
+// past the row pass head = true, own = false). `own` is the lane's own u01(r.x) < p. Returns the
+// decision of the lane's head: the highest head at or below it, or, if the window has none
+// there, the last head of the windows before (`carry`, which this call updates).
+__device__ inline bool word_masked(bool head, bool own, int lane, bool& carry) {
+  const uint64_t heads = __ballot(head);
+  const uint64_t dec = __ballot(own);
+  const uint64_t below = heads & (~0ull >> (63 - lane));
+  bool m = carry;
+  if (below) m = (dec >> (63 - __clzll((long long)below))) & 1;
+  if (heads) carry = (dec >> (63 - __clzll((long long)heads))) & 1;
+  return m;
 }
 
 struct EncodeArgs {
@@ -138,7 +176,14 @@ constexpr int kEncWaves = 4;
 
 // One wave per sample; the row is staged in LDS (ids, labels as int32) in two barrier-separated
 // phases so that every output element is written exactly once, coalesced.
-__global__ void __launch_bounds__(64 * kEncWaves) encode_kernel(EncodeArgs E) {
+// WW: the fused masking is whole-word and the arguments carry the continuation bitmap; the
+// plain instantiation is the kernel as it was, arguments and code.
+struct EncodeWwArgs : EncodeArgs {
+  ContBits cont;
+};
+template <bool WW>
+__global__ void __launch_bounds__(64 * kEncWaves)
+encode_kernel(std::conditional_t<WW, EncodeWwArgs, EncodeArgs> E) {
   extern __shared__ __attribute__((aligned(16))) int32_t srow[];
   const int w = wave_id(), lane = threadIdx.x & 63;
   const int b = blockIdx.x * kEncWaves + w;
@@ -179,6 +224,29 @@ __global__ void __launch_bounds__(64 * kEncWaves) encode_kernel(EncodeArgs E) {
   __syncthreads();
   if (!active) return;
   const int64_t row = (int64_t)b * E.L;
+  if constexpr (WW) {
+    // windows of 64 slots up to a multiple of 64, the tail predicated: every lane reaches the
+    // ballots of word_masked
+    bool carry = false;
+    for (int32_t x0 = 0; x0 < E.L; x0 += 64) {
+      const int32_t x = x0 + lane;
+      const bool in = x < E.L;
+      const bool special = x == 0 || x == na + 1 || x >= end - 1;
+      const bool prev_special = x <= 1 || x - 1 == na + 1 || x - 1 >= end - 1;  // of slot x - 1
+      const int32_t id = in ? sid[x] : 0;
+      const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
+      const uint4 r = mask_draw(E.draw, row + x);
+      const bool m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
+      if (in) {
+        int64_t lab;
+        E.input_ids[row + x] = mask_apply(E.draw, r, !special && m, id, &lab);
+        E.labels[row + x] = lab;
+        E.token_type_ids[row + x] = (x >= na + 2 && x < end) ? 1 : 0;
+        E.attention_mask[row + x] = x < end ? 1 : 0;
+      }
+    }
+    return;
+  }
   for (int32_t x = lane; x < E.L; x += 64) {
     const bool special = x == 0 || x == na + 1 || x >= end - 1;
     if (E.fused_mask) {
@@ -249,6 +317,37 @@ __global__ void __launch_bounds__(256) mask_kernel(MaskArgs M) {
   else if (rnd) M.ids[i] = M.r_words[i];
 }
 
+constexpr int kWwWaves = 4;
+
+// Whole-word lddl_mask_dynamic: one wave per row (a word never leaves its row), 64-slot windows.
+// The special flag of slot x - 1 comes from the lane below, across windows from lane 63.
+__global__ void __launch_bounds__(64 * kWwWaves) mask_ww_kernel(MaskArgs M, ContBits C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * kWwWaves + wave_id();
+  if (b >= M.B) return;  // the whole wave
+  const MaskDraw D{M.p, M.ignore_index, M.mask_id, M.vocab_len, M.seed, M.counter};
+  bool carry = false;
+  int last_special = 1;  // slot 0 has no slot before it: never a continuation
+  for (int64_t x0 = 0; x0 < M.L; x0 += 64) {
+    const int64_t x = x0 + lane, i = b * M.L + x;
+    const bool in = x < M.L;
+    const int64_t id = in ? M.ids[i] : 0;
+    const bool special = !in || mask_special(M, i, b, x, id);
+    const int up = __shfl_up((int)special, 1, 64);
+    const bool prev_special = lane == 0 ? last_special != 0 : up != 0;
+    last_special = __shfl((int)special, 63, 64);
+    const bool cont = !special && !prev_special && cont_id(C, id);
+    const uint4 r = mask_draw(D, i);
+    const bool m = word_masked(!cont, u01(r.x) < D.p, lane, carry);
+    if (in) {
+      int64_t lab;
+      const int64_t out = mask_apply(D, r, !special && m, id, &lab);
+      M.labels[i] = lab;
+      if (out != id) M.ids[i] = out;
+    }
+  }
+}
+
 }  // namespace
 }  // namespace lddl
 
@@ -270,7 +369,7 @@ static int collate_encode(lddl_ctx* c, void* stream, const uint8_t* d_bytes, con
                d_pos, d_pos_off, d_labels, d_loss_mask, ignore_index, 0, {}};
   const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;
   if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", seq_len);
-  hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
+  hipLaunchKernelGGL(encode_kernel<false>, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
                      dim3(64 * kEncWaves), lds, as_stream(stream), E);
   LDDL_HIP(hipGetLastError());
   return 0;
@@ -352,7 +451,55 @@ extern "C" int lddl_collate_encode_masked(lddl_ctx* c, void* stream, const uint8
                         counter}};
   const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;
   if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", seq_len);
-  hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
+  hipLaunchKernelGGL(encode_kernel<false>, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
+                     dim3(64 * kEncWaves), lds, as_stream(stream), E);
+  LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int lddl_mask_dynamic_ww(lddl_ctx* c, void* stream, int64_t* d_input_ids,
+                                    int64_t* d_labels, const int64_t* d_special_tokens_mask,
+                                    const int32_t* d_na, const int32_t* d_nb, int64_t batch,
+                                    int64_t seq_len, float mlm_probability, int64_t ignore_index,
+                                    int64_t vocab_len, uint64_t seed, uint64_t counter) {
+  if (!c) LDDL_FAIL(-1, "null ctx");
+  if (!d_special_tokens_mask && (!d_na != !d_nb)) LDDL_FAIL(-1, "need both lengths or neither");
+  if (c->tab.special_id[kMask] < 0) LDDL_FAIL(-1, "vocab has no [MASK]");
+  if (batch <= 0 || seq_len <= 0) return 0;
+  MaskArgs M{d_input_ids, d_labels, d_special_tokens_mask, d_na, d_nb, batch, seq_len,
+             mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, {}, seed, counter,
+             nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < kNumSpecial; ++k) M.special_ids[k] = c->tab.special_id[k];
+  hipLaunchKernelGGL(mask_ww_kernel, dim3((unsigned)((batch + kWwWaves - 1) / kWwWaves)),
+                     dim3(64 * kWwWaves), 0, as_stream(stream), M,
+                     ContBits{c->d_cont_bits, c->vocab_size});
+  LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int lddl_collate_encode_masked_ww(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
+                                             const int64_t* d_a_off, const int64_t* d_b_off,
+                                             const int32_t* d_na, const int32_t* d_nb,
+                                             int32_t batch, int32_t seq_len, int64_t* d_input_ids,
+                                             int64_t* d_token_type_ids, int64_t* d_attention_mask,
+                                             int64_t* d_labels, float mlm_probability,
+                                             int64_t ignore_index, int64_t vocab_len, uint64_t seed,
+                                             uint64_t counter) {
+  if (!c) LDDL_FAIL(-1, "null ctx");
+  if (batch <= 0 || seq_len <= 0) return 0;
+  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0 || c->tab.special_id[kMask] < 0)
+    LDDL_FAIL(-1, "vocab needs [CLS], [SEP] and [MASK]");
+  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels)
+    LDDL_FAIL(-1, "null output");
+  EncodeWwArgs E{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len, d_input_ids,
+                  d_token_type_ids, d_attention_mask, nullptr, nullptr, nullptr, nullptr, nullptr,
+                  d_labels, nullptr, ignore_index, 1,
+                  MaskDraw{mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len,
+                           seed, counter}},
+                 ContBits{c->d_cont_bits, c->vocab_size}};
+  const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;
+  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", seq_len);
+  hipLaunchKernelGGL(encode_kernel<true>, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
                      dim3(64 * kEncWaves), lds, as_stream(stream), E);
   LDDL_HIP(hipGetLastError());
   return 0;

@@ -22,6 +22,9 @@ struct lddl_ctx {
   int64_t* d_render_off = nullptr;  // token i = d_render[off[i] .. off[i+1])
   uint32_t* d_bloom = nullptr;
   uint64_t* d_vlong = nullptr;
+  // one bit per id: the vocab line is a continuation piece ("##" and more). Whole-word masking
+  // only (collate.hip); not part of Tables
+  uint32_t* d_cont_bits = nullptr;
   int32_t vocab_size = 0;
   // bytes per token id in the pair tables (dense kept tokens, sample tokens, labels): 2 when every
   // id fits uint16 with two values to spare for the gather's decision table (vocab_size <=

@@ -139,6 +139,9 @@ extern "C" int lddl_ctx_create(int device, const uint8_t* norm_table, int64_t ta
     const int len = (int)(voff[i + 1] - voff[i]);
     memcpy(reinterpret_cast<uint8_t*>(vlong.data() + 4 * (size_t)i), vbytes.data() + voff[i], std::min(len, 32));
   }
+  std::vector<uint32_t> cont_bits(((size_t)V + 31) / 32, 0u);
+  for (int32_t i = 0; i < V; ++i)
+    if (cont[i]) cont_bits[i >> 5] |= 1u << (i & 31);
   const uint8_t* l1 = norm_table + 20;
   const uint8_t* pages = l1 + 2 * 4352;
   const uint8_t* pool = pages + 4 * 256 * (int64_t)n_pages;
@@ -150,7 +153,8 @@ extern "C" int lddl_ctx_create(int device, const uint8_t* norm_table, int64_t ta
       (rc = upload(&c->d_render, render.data(), render.size())) ||
       (rc = upload(&c->d_render_off, roff.data(), sizeof(int64_t) * roff.size())) ||
       (rc = upload(&c->d_bloom, bloom.data(), sizeof(uint32_t) * bloom.size())) ||
-      (rc = upload(&c->d_vlong, vlong.data(), sizeof(uint64_t) * vlong.size()))) {
+      (rc = upload(&c->d_vlong, vlong.data(), sizeof(uint64_t) * vlong.size())) ||
+      (rc = upload(&c->d_cont_bits, cont_bits.data(), sizeof(uint32_t) * cont_bits.size()))) {
     lddl_ctx_destroy(c);
     return rc;
   }
@@ -198,7 +202,7 @@ extern "C" int lddl_ctx_destroy(lddl_ctx* c) {
   lddl_punkt_release(c);
   for (void* p : {(void*)c->d_l1, (void*)c->d_pages, (void*)c->d_pool, (void*)c->d_vhash,
                   (void*)c->d_vbytes, (void*)c->d_voff, (void*)c->d_render, (void*)c->d_render_off,
-                  (void*)c->d_bloom, (void*)c->d_vlong})
+                  (void*)c->d_bloom, (void*)c->d_vlong, (void*)c->d_cont_bits})
     if (p) (void)hipFree(p);
   delete c;
   return 0;

@@ -106,7 +106,7 @@ def _to_encoded_inputs(batch, tokenizer, sequence_length_alignment=8, ignore_ind
 
 
 def _mask_tokens(inputs, special_tokens_mask=None, tokenizer=None, mlm_probability=0.15,
-                 ignore_index=-1, seed=12345, counter=0, replay=None):
+                 ignore_index=-1, seed=12345, counter=0, replay=None, whole_word=False):
     """lddl/torch/bert.py:152-196 on the GPU; masks `inputs` in place and returns
     (inputs, labels).
 
@@ -114,7 +114,15 @@ def _mask_tokens(inputs, special_tokens_mask=None, tokenizer=None, mlm_probabili
     tokenizer.get_special_tokens_mask(ids, already_has_special_tokens=True) (bert.py:167-172).
     Native mode draws from Philox keyed by (seed, counter): pass a new counter per batch.
     replay = dict(masked=, replaced=, random=, words=) applies captured torch draws exactly.
+
+    whole_word=True (past the reference) masks a word, i.e. a head and the "##"
+    continuation ids behind it, as a unit: every slot of the word takes the head's Bernoulli(p)
+    draw, while 80 / 10 / 10 and the random id stay each slot's own. Each non-special token is
+    still masked with probability p, and a row without continuation ids comes out bit-identical
+    to whole_word=False. Native draws only: with `replay` it raises ValueError.
     """
+    if whole_word and replay is not None:
+        raise ValueError('whole_word=True draws natively; it cannot replay captured masks')
     ctx = tokenizer
     assert inputs.is_cuda and inputs.dtype == torch.long and inputs.is_contiguous()
     B, L = inputs.shape
@@ -122,6 +130,11 @@ def _mask_tokens(inputs, special_tokens_mask=None, tokenizer=None, mlm_probabili
     stm = special_tokens_mask
     if stm is not None:
         stm = stm.to(device=inputs.device, dtype=torch.long).contiguous()
+    if whole_word:
+        check(lib.lddl_mask_dynamic_ww(ctx.handle, _stream(), _ptr(inputs), _ptr(labels), _ptr(stm),
+                                       None, None, B, L, float(mlm_probability), ignore_index,
+                                       len(ctx), seed, counter))
+        return inputs, labels
     r = [None] * 4
     if replay is not None:
         r = [replay['masked'].to(inputs.device, torch.uint8).contiguous(),
@@ -135,7 +148,7 @@ def _mask_tokens(inputs, special_tokens_mask=None, tokenizer=None, mlm_probabili
 
 
 def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=None, events=None,
-                  stager=None, loss_mask=False):
+                  stager=None, loss_mask=False, whole_word=False):
     """`_to_encoded_inputs` on an already packed batch (main process, GPU).
 
     loss_mask=True is lddl.torch_mp's `_to_encoded_inputs`: a static-masking batch also gets
@@ -144,8 +157,10 @@ def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=No
 
     mask = (mlm_probability, seed, counter) on a dynamic-masking batch runs `_mask_tokens` fused
     into the same kernel (lddl_collate_encode_masked) and returns `labels` instead of
-    `special_tokens_mask`. events: optional pair of torch.cuda.Event recorded around the
-    encode kernel (timing). stager: the HostStager whose pinned ring carries the batch to the
+    `special_tokens_mask`; with whole_word=True the fused masking is whole-word
+    (lddl_collate_encode_masked_ww, see `_mask_tokens`), and without `mask` or on a
+    static-masking batch whole_word has no effect. events: optional pair of torch.cuda.Event
+    recorded around the encode kernel (timing). stager: the HostStager whose pinned ring carries the batch to the
     device (default: one per device)."""
     dev = ctx.device
     B = len(pk)
@@ -169,7 +184,8 @@ def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=No
         labels = torch.empty(B, L, dtype=torch.long, device=dev)
         if events is not None:
             events[0].record()
-        check(lib.lddl_collate_encode_masked(
+        fused = lib.lddl_collate_encode_masked_ww if whole_word else lib.lddl_collate_encode_masked
+        check(fused(
             ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b), _ptr(d_na), _ptr(d_nb), B,
             L, _ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']),
             _ptr(labels), float(p), ignore_index, len(ctx), seed, counter))
@@ -228,11 +244,14 @@ class GPUCollateLoader:
     """Iterates a torch DataLoader of PackedBatch and finishes the collate on the GPU."""
 
     def __init__(self, loader, ctx, mlm_probability, ignore_index, sequence_length_alignment,
-                 extra_collate, seed, start_epoch=0, stager=None, loss_mask=False):
+                 extra_collate, seed, start_epoch=0, stager=None, loss_mask=False,
+                 whole_word=False):
         self._loader = loader
         # lddl.torch_mp: static batches carry masked_lm_positions (lddl.torch calls encode_packed
         # exactly as before)
         self._mp = {'loss_mask': True} if loss_mask else {}
+        if whole_word:  # dynamic masking by whole words (DESIGN §15): likewise passed only if set
+            self._mp['whole_word'] = True
         self._lazy = ctx if isinstance(ctx, _LazyContext) else None
         self._ctx_obj = None if self._lazy is not None else ctx
         self._mlm = mlm_probability
@@ -243,6 +262,7 @@ class GPUCollateLoader:
         self._epoch = start_epoch    # counter = epoch << 32 | batch: no stream repeats across
         self._counter = start_epoch << 32  # epochs, and a resumed run continues, not replays
         self._stager = stager
+        self._whole_word = whole_word
         self.stats = None  # dict(pack_s=[], blob_bytes=[], events=[], slots=[]): record timings
 
     @property
@@ -269,6 +289,9 @@ class GPUCollateLoader:
 
     def _batches(self, it):
         for pk in it:
+            if self._whole_word and pk.static:
+                raise ValueError('whole_word_masking=True needs a dynamic-masking dataset: these '
+                                 'samples were masked by the preprocessor')
             ctx = self._ctx
             ev = None
             if self.stats is not None:
@@ -308,9 +331,14 @@ def get_bert_pretrain_data_loader(path, local_rank=0, shuffle_buffer_size=16384,
                                   vocab_file=None, tokenizer_kwargs={}, data_loader_class=DataLoader,
                                   data_loader_kwargs={}, mlm_probability=0.15, base_seed=12345,
                                   log_dir=None, log_level=logging.INFO, return_raw_samples=False,
-                                  start_epoch=0, sequence_length_alignment=8, ignore_index=-1):
-    """Same signature, arguments and yielded dicts as lddl.torch.get_bert_pretrain_data_loader
+                                  start_epoch=0, sequence_length_alignment=8, ignore_index=-1,
+                                  whole_word_masking=False):
+    """Same arguments and yielded dicts as lddl.torch.get_bert_pretrain_data_loader
     (lddl/torch/bert.py:199-413); the tensors are on the current cuda device.
+
+    whole_word_masking=True (one keyword past the reference's signature) makes the dynamic
+    masking whole-word (`_mask_tokens(whole_word=True)`); a static-masking dataset then raises
+    ValueError at its first batch, and with return_raw_samples=True the option is ignored.
 
     tokenizer_class is accepted for compatibility (BertTokenizerFast / BertTokenizer or None):
     the vocab file is loaded into a lddl_amd Context (vocab hash in HBM). vocab_file must be a
@@ -319,14 +347,15 @@ def get_bert_pretrain_data_loader(path, local_rank=0, shuffle_buffer_size=16384,
         path, local_rank, None, shuffle_buffer_size, shuffle_buffer_warmup_factor,
         tokenizer_class, vocab_file, tokenizer_kwargs, data_loader_class, data_loader_kwargs,
         mlm_probability, base_seed, log_dir, log_level, return_raw_samples, start_epoch,
-        sequence_length_alignment, ignore_index)
+        sequence_length_alignment, ignore_index, whole_word_masking)
 
 
 def _bert_pretrain_data_loader(path, local_rank, dp_rank, shuffle_buffer_size,
                                shuffle_buffer_warmup_factor, tokenizer_class, vocab_file,
                                tokenizer_kwargs, data_loader_class, data_loader_kwargs,
                                mlm_probability, base_seed, log_dir, log_level, return_raw_samples,
-                               start_epoch, sequence_length_alignment, ignore_index):
+                               start_epoch, sequence_length_alignment, ignore_index,
+                               whole_word_masking=False):
     """The loader of lddl.torch (dp_rank None) and of lddl.torch_mp (dp_rank given: files are
     strided and workers seeded by data-parallel rank, static batches carry the loss mask, and the
     dynamic-masking key is the group's, so all ranks of a group yield the same batches)."""
@@ -348,6 +377,7 @@ def _bert_pretrain_data_loader(path, local_rank, dp_rank, shuffle_buffer_size,
                          logging.ERROR, logging.CRITICAL}
     assert isinstance(return_raw_samples, bool)
     assert isinstance(start_epoch, int)
+    assert isinstance(whole_word_masking, bool)
     if not os.path.isfile(vocab_file):
         raise FileNotFoundError('vocab_file {!r}: a local vocab.txt is required (offline)'.format(
             vocab_file))
@@ -375,7 +405,7 @@ def _bert_pretrain_data_loader(path, local_rank, dp_rank, shuffle_buffer_size,
         return GPUCollateLoader(dl, ctx, mlm_probability, ignore_index,
                                 sequence_length_alignment, extra_collate,
                                 mask_seed(base_seed, mask_rank, bin_id), start_epoch, stager,
-                                loss_mask=dp_rank is not None)
+                                loss_mask=dp_rank is not None, whole_word=whole_word_masking)
 
     paths = get_all_parquets_under(path)
     bin_ids = get_all_bin_ids(paths)

@@ -36,14 +36,17 @@ def get_bert_pretrain_data_loader(path, local_rank=0, dp_rank=0, shuffle_buffer_
                                   vocab_file=None, tokenizer_kwargs={}, data_loader_class=DataLoader,
                                   data_loader_kwargs={}, mlm_probability=0.15, base_seed=12345,
                                   log_dir=None, log_level=logging.INFO, return_raw_samples=False,
-                                  start_epoch=0, sequence_length_alignment=8, ignore_index=-1):
-    """Same signature, arguments and yielded dicts as
+                                  start_epoch=0, sequence_length_alignment=8, ignore_index=-1,
+                                  whole_word_masking=False):
+    """Same arguments and yielded dicts as
     lddl.torch_mp.get_bert_pretrain_data_loader (lddl/torch_mp/bert.py:213-429); the tensors are
     on the current cuda device. dp_rank is this process's data-parallel rank, e.g. Megatron's
-    `mpu.get_data_parallel_rank()`; the number of groups is max(dp_rank) + 1 over the world."""
+    `mpu.get_data_parallel_rank()`; the number of groups is max(dp_rank) + 1 over the world.
+    whole_word_masking: as in lddl_amd.torch (one keyword past the reference's signature); the
+    key is still the dp_rank group's, so the ranks of a group still yield identical batches."""
     assert isinstance(dp_rank, int) and dp_rank >= 0
     return _bert._bert_pretrain_data_loader(
         path, local_rank, dp_rank, shuffle_buffer_size, shuffle_buffer_warmup_factor,
         tokenizer_class, vocab_file, tokenizer_kwargs, data_loader_class, data_loader_kwargs,
         mlm_probability, base_seed, log_dir, log_level, return_raw_samples, start_epoch,
-        sequence_length_alignment, ignore_index)
+        sequence_length_alignment, ignore_index, whole_word_masking)
