@@ -233,11 +233,49 @@ int lddl_pairs_plan(lddl_ctx* ctx, void* stream, const lddl_pair_params* params,
 int lddl_pairs_emit(lddl_pairs* plan, void* stream, void* d_tokens, int64_t* d_tok_off,
                     int32_t* d_len_a, uint8_t* d_is_rn, uint16_t* d_pos, void* d_lab,
                     int64_t* d_pos_off);
+/* The same plan and gather in two halves, so that the caller's gather of the first partitions'
+ * pairs overlaps the planner. With rng = LDDL_RNG_REPLAY and static masking, a batch of more
+ * partitions than the device holds planner workgroups is planned in two partition ranges: the
+ * head on `stream`, the tail on a side stream of the context (ordered by events only). The pairs
+ * of the head are a prefix of the output and final once the head is planned.
+ *   lddl_pairs_plan_head: inputs as lddl_pairs_plan. head[8] = {split, head pairs, head tokens,
+ *     head masked positions, suggested capacity for pairs, for tokens, for masked positions, 0}.
+ *     split = 0: the plan is complete and one range; call lddl_pairs_plan_tail for the counts and
+ *     lddl_pairs_emit. split = 1: the tail's planner is still running. The capacities are the
+ *     head's counts scaled by kept tokens (all) / kept tokens (head) plus a margin: outputs
+ *     allocated at them usually hold the whole plan.
+ *   lddl_pairs_emit_head: output pairs [0, head pairs) into the caller's buffers (arguments as
+ *     lddl_pairs_emit, on the stream of lddl_pairs_plan_head); only between the two plan calls.
+ *   lddl_pairs_plan_tail: waits for the tail range, plans its layout and returns counts[5] as
+ *     lddl_pairs_plan does. *head_valid = 0 when the head range's output is void: the plan did
+ *     not split, or a mask pool overflowed and everything was planned again in one range (the
+ *     result is the same; what lddl_pairs_emit_head wrote must be discarded and lddl_pairs_emit
+ *     called). Runs on the stream of lddl_pairs_plan_head.
+ *   lddl_pairs_emit_tail: output pairs [head pairs, pairs) into the same buffers; needs
+ *     *head_valid = 1. The offset tables' entries are absolute, so together the two calls write
+ *     exactly what lddl_pairs_emit writes.
+ * lddl_pairs_plan = lddl_pairs_plan_head + lddl_pairs_plan_tail. LDDL_PLAN_SPLIT (environment,
+ * A/B): unset or -1 = automatic, 0 = never split, k > 0 = a head of exactly min(k, n_part)
+ * partitions; any other value fails the call. */
+int lddl_pairs_plan_head(lddl_ctx* ctx, void* stream, const lddl_pair_params* params,
+                         const int64_t* d_sent_off, const int32_t* d_ids, const int32_t* d_sent_len,
+                         int64_t n_sent, const int64_t* d_doc_sent_off, int64_t n_doc,
+                         const int64_t* d_part_doc_off, const int64_t* d_part_seed, int64_t n_part,
+                         lddl_pairs** out, int64_t* head);
+int lddl_pairs_emit_head(lddl_pairs* plan, void* stream, void* d_tokens, int64_t* d_tok_off,
+                         int32_t* d_len_a, uint8_t* d_is_rn, uint16_t* d_pos, void* d_lab,
+                         int64_t* d_pos_off);
+int lddl_pairs_plan_tail(lddl_pairs* plan, int64_t* counts, int32_t* head_valid);
+int lddl_pairs_emit_tail(lddl_pairs* plan, void* stream, void* d_tokens, int64_t* d_tok_off,
+                         int32_t* d_len_a, uint8_t* d_is_rn, uint16_t* d_pos, void* d_lab,
+                         int64_t* d_pos_off);
 int lddl_pairs_destroy(lddl_pairs* plan, void* stream);
 /* d_part_pair_off[n_part + 1]: first output pair of each partition (pairs are emitted in
  * partition order), i.e. the row ranges of the reference's per-partition outputs. */
 int lddl_pairs_part_offsets(lddl_pairs* plan, void* stream, int64_t* d_part_pair_off);
-/* Device time (ms, HIP events on the plan's stream) of the planner kernel of lddl_pairs_plan. */
+/* Device time (ms, HIP events on the plan's stream) of the planner kernel of lddl_pairs_plan:
+ * from its first launch until its last partition range is complete (a split plan: after
+ * lddl_pairs_plan_tail; the span includes what ran on the stream under the tail range). */
 int lddl_pairs_plan_ms(const lddl_pairs* plan, float* ms);
 
 /* ---------------------------------------------------------------------------------------------

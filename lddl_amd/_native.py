@@ -52,6 +52,12 @@ SIGNATURES = {
     'lddl_pairs_plan': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
                                        c_vp, c_i64, ctypes.POINTER(c_vp), c_vp]),
     'lddl_pairs_emit': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # the plan and the gather in two halves (a split replay plan: head range, then tail range)
+    'lddl_pairs_plan_head': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64,
+                                            c_vp, c_vp, c_i64, ctypes.POINTER(c_vp), c_vp]),
+    'lddl_pairs_emit_head': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'lddl_pairs_plan_tail': (ctypes.c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_int32)]),
+    'lddl_pairs_emit_tail': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'lddl_pairs_destroy': (ctypes.c_int, [c_vp, c_vp]),
     'lddl_pairs_part_offsets': (ctypes.c_int, [c_vp, c_vp, c_vp]),
     'lddl_pairs_plan_ms': (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_float)]),

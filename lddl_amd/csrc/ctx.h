@@ -35,6 +35,9 @@ struct lddl_ctx {
   lddl::DevArena arena;             // per-call temporaries (pair plans)
   void* punkt = nullptr;            // lddl_punkt_state (segment.hip), created by lddl_punkt_set_params
   void* bart = nullptr;             // lddl_bart_state (bart.hip), created by lddl_bart_count
+  // the pair planner's side stream (pairs.hip: the tail range of a split plan), created on first
+  // use: non-blocking, lowest priority
+  hipStream_t plan_side = nullptr;
 };
 extern "C" void lddl_punkt_release(lddl_ctx* c);
 extern "C" void lddl_bart_release(lddl_ctx* c);

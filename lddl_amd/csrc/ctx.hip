@@ -200,6 +200,10 @@ extern "C" int lddl_ctx_destroy(lddl_ctx* c) {
   (void)hipSetDevice(c->device);
   lddl_bart_release(c);
   lddl_punkt_release(c);
+  if (c->plan_side) {
+    (void)hipStreamSynchronize(c->plan_side);
+    (void)hipStreamDestroy(c->plan_side);
+  }
   for (void* p : {(void*)c->d_l1, (void*)c->d_pages, (void*)c->d_pool, (void*)c->d_vhash,
                   (void*)c->d_vbytes, (void*)c->d_voff, (void*)c->d_render, (void*)c->d_render_off,
                   (void*)c->d_bloom, (void*)c->d_vlong, (void*)c->d_cont_bits})

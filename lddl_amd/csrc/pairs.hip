@@ -31,6 +31,7 @@
 #include "ctx.h"
 #include "device.h"
 #include "lddl_amd.h"
+#include "plan_split.h"
 #include "scan.h"
 
 namespace lddl {
@@ -511,6 +512,10 @@ struct PlanArgs {
   IdPtr dense;              // out: kept tokens, packed (densify_group)
   int64_t n_kept_sent;
   int32_t n_part, n_dense_wg;  // workgroups >= n_part fill `dense`
+  // one launch plans partitions [p0, p0 + n_part) (a split plan: a head and a tail launch); its
+  // dense workgroups pack kept sentences [*dense_lo, n_kept_sent) (null: from 0)
+  int32_t p0;
+  const int64_t* dense_lo;
   const int64_t* part_seed;
   // params
   int32_t seq, dup, masking, vocab_size, cls_id, sep_id, mask_id, max_pred;
@@ -680,18 +685,19 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint32_t* s_mt = reinterpret_cast<uint32_t*>(smem);
   int32_t* s_doc = reinterpret_cast<int32_t*>(s_mt + kN + kLook);  // [kDocLds + 1]
-  const int p = blockIdx.x;
   const int lane = threadIdx.x;
   const bool leader = lane == 0;
-  if (p >= A.n_part) {
+  if ((int)blockIdx.x >= A.n_part) {
     // Workgroups past the partitions pack `dense` (what densify_kernel would do after this
     // launch). Dispatched in order, they start as the last partitions' waves are placed and
     // run in the slots the planner's tail leaves idle (a separate launch before or beside the
     // planner delays its dispatch).
-    for (int64_t g = p - A.n_part; g * 64 < A.n_kept_sent; g += A.n_dense_wg)
-      densify_group(g * 64, A.ks_start, A.ks_len, A.kscan, A.n_kept_sent, A.ids, A.dense);
+    const int64_t k_lo = A.dense_lo ? *A.dense_lo : 0;
+    for (int64_t g = (int)blockIdx.x - A.n_part; k_lo + g * 64 < A.n_kept_sent; g += A.n_dense_wg)
+      densify_group(k_lo + g * 64, A.ks_start, A.ks_len, A.kscan, A.n_kept_sent, A.ids, A.dense);
     return;
   }
+  const int p = A.p0 + (int)blockIdx.x;
 #ifdef LDDL_STAMPS
   uint64_t st_acc[kStampRegions] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -1604,6 +1610,38 @@ __global__ void __launch_bounds__(256) densify_kernel(const int64_t* __restrict_
   densify_group(k0, ks_start, ks_len, kscan, n, ids, dense);
 }
 
+// Split plan: the first kept sentence of the tail range's partitions (= the end of the head's)
+// and the kept tokens before it. info[0] bounds the two ranges' dense packing, info[1] scales
+// the head's counts to the suggested output capacities.
+__global__ void split_info_kernel(const int64_t* kp_off, const int64_t* kd_off, const int64_t* kscan,
+                                  int64_t s, int64_t* info) {
+  const int64_t k = kd_off[kp_off[s]];
+  info[0] = k;
+  info[1] = kscan[k];
+}
+
+// densify_kernel over kept sentences [0, *n_ptr): the head range of a split plan (the launch
+// covers all kept sentences; the workgroups past the bound leave at once)
+__global__ void __launch_bounds__(256) densify_head_kernel(const int64_t* __restrict__ ks_start,
+                                                           const int32_t* __restrict__ ks_len,
+                                                           const int64_t* __restrict__ kscan,
+                                                           const int64_t* __restrict__ n_ptr,
+                                                           const int32_t* __restrict__ ids,
+                                                           IdPtr dense) {
+  const int64_t n = *n_ptr;
+  const int64_t k0 = ((int64_t)blockIdx.x * 4 + wave_id()) * 64;
+  if (k0 >= n) return;
+  densify_group(k0, ks_start, ks_len, kscan, n, ids, dense);
+}
+
+// part_base[s + 1 + i] = head_pairs + rel[i + 1], i in [0, n): the tail range's partitions in
+// the plan's one table of first output pairs (part_base[s] = head_pairs came with the head)
+__global__ void tail_part_base_kernel(const int64_t* rel, int64_t n, int64_t head_pairs,
+                                      int64_t* part_base_s) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) part_base_s[1 + i] = head_pairs + rel[i + 1];
+}
+
 
 struct GatherArgs {
   const void* dense;     // kept tokens, packed (IdT)
@@ -1612,9 +1650,14 @@ struct GatherArgs {
   const uint16_t* mpos;
   const int32_t* mtok;
   int32_t masking;
+  // one launch gathers one range of output pairs: q counts from the range's first pair, rec /
+  // tok_off / pos_off are the range's tables (offsets relative to its first token / mask) and
+  // tok_base / pos_base the tokens / masks of the pairs before it; len_a, is_rn and the offset
+  // copies point at the range's first pair
   int64_t n_pairs;
   const int64_t* tok_off;
   const int64_t* pos_off;
+  int64_t tok_base, pos_base;
   void* out_tok;  // IdT
   int32_t* len_a;
   uint8_t* is_rn;
@@ -1949,8 +1992,8 @@ __global__ void __launch_bounds__(64 * kGWaves, 1) gather_kernel(GatherArgs G, G
     const int64_t q = q0 + 2 * k + h;
     const bool act = q < G.n_pairs;
     rc[k] = act ? G.rec[q] : GatherRec{0, 0, 0, 0, 0, 0, 0};
-    tof[k] = act ? G.tok_off[q] : 0;
-    po[k] = (G.masking && act) ? G.pos_off[q] : 0;
+    tof[k] = act ? G.tok_base + G.tok_off[q] : 0;
+    po[k] = (G.masking && act) ? G.pos_base + G.pos_off[q] : 0;
   }
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -2140,8 +2183,8 @@ __global__ void __launch_bounds__(64 * kGWaves, 1) gather16_kernel(GatherArgs G,
   const int64_t q = (wg * kGWaves + w) * PW + qw;
   const bool act = q < G.n_pairs;
   const GatherRec r = act ? G.rec[q] : GatherRec{0, 0, 0, 0, 0, 0, 0};
-  const int64_t tof = act ? G.tok_off[q] : 0;
-  const int64_t po = (G.masking && act) ? G.pos_off[q] : 0;
+  const int64_t tof = act ? G.tok_base + G.tok_off[q] : 0;
+  const int64_t po = (G.masking && act) ? G.pos_base + G.pos_off[q] : 0;
   const int32_t na = r.na, nb = r.nb_rn & 0x7FFFFFFF, n = na + nb;
   const int32_t nm = G.masking ? r.nm : 0;
   const int64_t mb = r.moff;
@@ -2253,6 +2296,66 @@ __global__ void __launch_bounds__(64 * kGWaves, 1) gather16_kernel(GatherArgs G,
 
 using namespace lddl;
 
+// A/B knobs of the mask replay, LDDL_FY_MODE / LW / RA / PF (what they select: resolve_masks)
+struct FyKnobs {
+  int mode, lw, ra, pf;
+};
+
+// What one planning stage hands to the next: the inputs of the call, host values read back, and
+// device temporaries that no later call on the plan reads. The temporaries come from `tmp`,
+// today the plan's own scope (they live until lddl_pairs_destroy); a scope local to
+// lddl_pairs_plan would return them when planning ends.
+// (A split plan keeps it between its head and tail calls, lddl_pairs::work.)
+struct PlanWork {
+  lddl_ctx* c;
+  const lddl_pair_params* prm;  // the plan's own copy (lddl_pairs::prm)
+  const int32_t* d_ids;
+  const int64_t* d_part_seed;
+  int64_t n_sent, n_part;
+  hipStream_t st;
+  ArenaScope& tmp;
+  FyKnobs fy;
+  int64_t split_knob = -1;  // LDDL_PLAN_SPLIT
+  // compact_inputs
+  int64_t* scratch = nullptr;  // scan scratch of the compaction and of the re-plan loop
+  int64_t n_kept_tok = 0;
+  unsigned long long max_docs = 0;  // kept documents of the largest partition
+  // plan_replay
+  int32_t* jseq = nullptr;
+  int64_t* part_npairs = nullptr;
+  SlotPool* spool = nullptr;
+  void* jpool = nullptr;
+  int64_t max_np = 1;  // pairs of the largest partition
+  // the planner launch and its pools, kept for the tail call and the re-plan
+  PlanArgs A{};
+  unsigned long long* pool_ctl = nullptr;  // [0] masks used, [1] overflow flag, [2] draws used, [3] max pairs
+  int64_t cap = 0, jcap = 0;
+  int32_t* mtok_try = nullptr;  // this attempt's pools
+  uint8_t* jpool_try = nullptr;
+  int64_t split = 0;            // partitions of the head range (0: one range)
+  int64_t* split_info = nullptr;  // split_info_kernel's two values, and their host copies
+  int64_t h_split_info[2] = {0, 0};
+  int64_t* tail_rel = nullptr;  // the tail partitions' first pairs, relative to the range
+  // shuffle_partitions
+  PairMaps M{nullptr, nullptr, nullptr, nullptr};
+  // layout
+  int2* pcnt = nullptr;
+  int64_t* scr2 = nullptr;
+#ifdef LDDL_STAMPS
+  uint64_t *d_stamps = nullptr, *d_tl = nullptr;
+#endif
+};
+
+// Output pairs of partitions [p0, p1) of a plan: pair q of the range is output pair pair0 + q,
+// its tokens start at tok0 + tok_off[q] and its masks at pos0 + pos_off[q].
+struct PairRange {
+  int64_t p0 = 0, p1 = 0;
+  int64_t n_pairs = 0, n_tokens = 0, n_masked = 0;
+  int64_t pair0 = 0, tok0 = 0, pos0 = 0;
+  GatherRec* rec = nullptr;  // per output pair (pair_prep_kernel / fy_resolve_kernel)
+  int64_t *tok_off = nullptr, *pos_off = nullptr;  // [n_pairs + 1]
+};
+
 // Device-resident plan of one batch of partitions (library-owned temporaries).
 struct lddl_pairs {
   int32_t masking = 0, max_pred = 0, seq = 0, cls_id = -1, sep_id = -1;
@@ -2269,21 +2372,35 @@ struct lddl_pairs {
   int32_t *order = nullptr, *nmask = nullptr, *mtok = nullptr;
   uint16_t* mpos = nullptr;
   int64_t* moff = nullptr;
-  int64_t *src = nullptr, *tok_off = nullptr, *pos_off = nullptr;
-  GatherRec* rec = nullptr;  // per output pair (pair_prep_kernel)
+  int64_t* src = nullptr;
+  // The output pairs' tables. One range covers the plan; a split replay plan has two, the head
+  // and the tail partitions' pairs, each with blocks sized by its own pair count.
+  PairRange rg[2];
+  int n_rg = 1;
   int64_t* part_base = nullptr;  // [n_part + 1] first output pair of each partition
-  hipEvent_t ev[2] = {nullptr, nullptr};  // around the last plan_replay_kernel launch
+  // first planner launch .. last planner range complete (on the planning stream, after the join)
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  // split plan: the tail launch runs on the context's side stream between ev_fork (recorded on
+  // the planning stream) and ev_join; until the planning stream has waited for ev_join
+  // (tail_pending) no block of the plan may go back
+  hipStream_t st;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  bool tail_pending = false;
+  bool head_valid = false;  // the head range's tables (and what was gathered from them) stand
+  lddl_pair_params prm{};
+  std::unique_ptr<PlanWork> work;  // between the head and the tail call
 
-  lddl_pairs(DevArena* arena, hipStream_t st) : mem(arena, st) {}
+  lddl_pairs(DevArena* arena, hipStream_t stream) : mem(arena, stream), st(stream) {}
+  // order `on` after the tail launch (before the plan's blocks go back on it)
+  void join(hipStream_t on) {
+    if (tail_pending) (void)hipStreamWaitEvent(on, ev_join, 0);
+    tail_pending = false;
+  }
   ~lddl_pairs() {
-    for (hipEvent_t e : ev)
+    join(st);  // (then `mem` gives the blocks back on st)
+    for (hipEvent_t e : {ev[0], ev[1], ev_fork, ev_join})
       if (e) (void)hipEventDestroy(e);
   }
-};
-
-// A/B knobs of the mask replay, LDDL_FY_MODE / LW / RA / PF (what they select: resolve_masks)
-struct FyKnobs {
-  int mode, lw, ra, pf;
 };
 
 static int env_int(const char* name, int dflt) {
@@ -2307,7 +2424,20 @@ static int read_fy_knobs(FyKnobs* k) {
   return 0;
 }
 
-static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKnobs* fy) {
+// A/B knob of the split replay plan, LDDL_PLAN_SPLIT: unset or -1 = automatic
+// (plan_split_point), 0 = one range, k > 0 = a head range of exactly min(k, n_part) partitions
+static int read_split_knob(int64_t* k) {
+  *k = -1;
+  const char* e = getenv("LDDL_PLAN_SPLIT");
+  if (!e) return 0;
+  char* end = nullptr;
+  const long long v = strtoll(e, &end, 10);
+  if (end == e || *end || v < -1) LDDL_FAIL(-1, "LDDL_PLAN_SPLIT must be -1 (auto), 0 or a partition count");
+  *k = v;
+  return 0;
+}
+
+static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKnobs* fy, int64_t* split_knob) {
   if (!c || !prm) LDDL_FAIL(-1, "null argument");
   if (prm->seq < 5 || prm->seq > 65535) LDDL_FAIL(-1, "target_seq_length %d out of range", prm->seq);
   if (prm->dup < 1) LDDL_FAIL(-1, "duplicate_factor must be >= 1");
@@ -2318,41 +2448,10 @@ static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKno
   if (prm->masking && (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0 ||
                        c->tab.special_id[kMask] < 0))
     LDDL_FAIL(-1, "static masking needs [CLS] [SEP] [MASK] in the vocab");
+  int rc;
+  if ((rc = read_split_knob(split_knob))) return rc;
   return read_fy_knobs(fy);
 }
-
-// What one planning stage hands to the next: the inputs of the call, host values read back, and
-// device temporaries that no later call on the plan reads. The temporaries come from `tmp`,
-// today the plan's own scope (they live until lddl_pairs_destroy); a scope local to
-// lddl_pairs_plan would return them when planning ends.
-struct PlanWork {
-  lddl_ctx* c;
-  const lddl_pair_params* prm;
-  const int32_t* d_ids;
-  const int64_t* d_part_seed;
-  int64_t n_sent, n_part;
-  hipStream_t st;
-  ArenaScope& tmp;
-  FyKnobs fy;
-  // compact_inputs
-  int64_t* scratch = nullptr;  // scan scratch of the compaction and of the re-plan loop
-  int64_t n_kept_tok = 0;
-  unsigned long long max_docs = 0;  // kept documents of the largest partition
-  // plan_replay
-  int32_t* jseq = nullptr;
-  int64_t* part_npairs = nullptr;
-  SlotPool* spool = nullptr;
-  void* jpool = nullptr;
-  int64_t max_np = 1;  // pairs of the largest partition
-  // shuffle_partitions
-  PairMaps M{nullptr, nullptr, nullptr, nullptr};
-  // layout
-  int2* pcnt = nullptr;
-  int64_t* scr2 = nullptr;
-#ifdef LDDL_STAMPS
-  uint64_t *d_stamps = nullptr, *d_tl = nullptr;
-#endif
-};
 
 // replay mode: the planner launch's tail workgroups pack `dense` (plan_replay_kernel)
 static bool dense_in_plan(const PlanWork& W) { return W.prm->rng == LDDL_RNG_REPLAY && W.n_part > 0; }
@@ -2424,35 +2523,43 @@ static int compact_inputs(lddl_pairs* P, PlanWork& W, const int64_t* d_sent_off,
 }
 
 // The gather records + output-order scans (tok_off, pos_off) of the plan's pairs.
-static int layout_alloc(lddl_pairs* P, PlanWork& W) {
-  const int64_t npairs = P->n_pairs;
+// (of one range; W.pcnt / W.scr2 are the range's temporaries)
+static int layout_alloc(lddl_pairs* P, PlanWork& W, PairRange& r) {
+  const int64_t npairs = r.n_pairs;
   int rc;
-  if ((rc = P->mem.take(&P->tok_off, npairs + 1)) || (rc = P->mem.take(&P->rec, npairs)) ||
+  if ((rc = P->mem.take(&r.tok_off, npairs + 1)) || (rc = P->mem.take(&r.rec, npairs)) ||
       (rc = W.tmp.take(&W.pcnt, npairs)) || (rc = W.tmp.take(&W.scr2, 2 * scan_scratch_elems(npairs))))
     return rc;
-  if (P->masking && (rc = P->mem.take(&P->pos_off, npairs + 1))) return rc;
+  if (P->masking && (rc = P->mem.take(&r.pos_off, npairs + 1))) return rc;
   return 0;
 }
 
-static int layout_scan(lddl_pairs* P, PlanWork& W) {  // tok_off (and pos_off) from the counts
+// tok_off (and pos_off) from the counts, then the range's totals (read with the caller's sync)
+static int layout_scan(lddl_pairs* P, PlanWork& W, PairRange& r) {
   if (P->masking)
-    LDDL_HIP(scan_exclusive2(PairCounts{W.pcnt}, P->n_pairs, P->tok_off, P->pos_off, W.scr2, W.st));
+    LDDL_HIP(scan_exclusive2(PairCounts{W.pcnt}, r.n_pairs, r.tok_off, r.pos_off, W.scr2, W.st));
   else
-    LDDL_HIP(scan_exclusive(PairTokens{W.pcnt}, P->n_pairs, P->tok_off, W.scr2, W.st));
+    LDDL_HIP(scan_exclusive(PairTokens{W.pcnt}, r.n_pairs, r.tok_off, W.scr2, W.st));
+  LDDL_HIP(hipMemcpyAsync(&r.n_tokens, r.tok_off + r.n_pairs, 8, hipMemcpyDeviceToHost, W.st));
+  if (P->masking)
+    LDDL_HIP(hipMemcpyAsync(&r.n_masked, r.pos_off + r.n_pairs, 8, hipMemcpyDeviceToHost, W.st));
   return 0;
 }
 
 // gather records from the output order (src): the native path, and replay without masking
 static int layout_pairs(lddl_pairs* P, PlanWork& W) {
   int rc;
-  if ((rc = layout_alloc(P, W))) return rc;
+  PairRange& r = P->rg[0];  // (always one range)
+  r.p1 = P->n_part;
+  r.n_pairs = P->n_pairs;
+  if ((rc = layout_alloc(P, W, r))) return rc;
   const int64_t npairs = P->n_pairs;
   if (npairs)
     hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, W.st,
                        P->src, npairs, P->desc, P->kscan, P->masking ? P->nmask : nullptr,
-                       P->moff, P->rec, W.pcnt);
+                       P->moff, r.rec, W.pcnt);
   LDDL_HIP(hipGetLastError());
-  return layout_scan(P, W);
+  return layout_scan(P, W, r);
 }
 
 // the kept corpus and the call's parameters, as both planners' kernels take them
@@ -2569,12 +2676,11 @@ static int plan_native(lddl_pairs* P, PlanWork& W) {
   return layout_pairs(P, W);
 }
 
-// LDDL_RNG_REPLAY planner: sizes the mask pools, launches plan_replay_kernel (between the plan's
-// two events) and, when a pool overflowed, once more with the exact sizes.
-static int plan_replay(lddl_pairs* P, PlanWork& W) {
+// LDDL_RNG_REPLAY planner, set-up: the slot tables, the planner's arguments (W.A) and the sizes
+// of the mask pools; decides whether the launch is split into a head and a tail range.
+static int plan_replay_setup(lddl_pairs* P, PlanWork& W) {
   const lddl_pair_params* prm = W.prm;
   const int64_t n_part = W.n_part;
-  hipStream_t st = W.st;
   if (prm->seq > 512) LDDL_FAIL(-1, "replay planner supports target_seq_length <= 512");
   const int64_t slots = (int64_t)prm->dup * P->n_kept_sent;
   int rc;
@@ -2582,7 +2688,7 @@ static int plan_replay(lddl_pairs* P, PlanWork& W) {
       (rc = W.tmp.take(&W.jseq, slots)) || (rc = W.tmp.take(&W.part_npairs, n_part + 1)))
     return rc;
   if (prm->masking && (rc = W.tmp.take(&W.spool, slots))) return rc;
-  PlanArgs A{};
+  PlanArgs& A = W.A;
   fill_plan_args(A, P, W);
   A.ks_start = P->ks_start;
   A.ids = W.d_ids;
@@ -2598,98 +2704,208 @@ static int plan_replay(lddl_pairs* P, PlanWork& W) {
 #ifdef LDDL_STAMPS
   if ((rc = W.tmp.take(&W.d_stamps, n_part * kStampRegions)) || (rc = W.tmp.take(&W.d_tl, n_part * 2)))
     return rc;
-  LDDL_HIP(hipMemsetAsync(W.d_stamps, 0, 8 * n_part * kStampRegions, st));
-  LDDL_HIP(hipMemsetAsync(W.d_tl, 0, 16 * n_part, st));
+  LDDL_HIP(hipMemsetAsync(W.d_stamps, 0, 8 * n_part * kStampRegions, W.st));
+  LDDL_HIP(hipMemsetAsync(W.d_tl, 0, 16 * n_part, W.st));
   A.stamps = W.d_stamps;
   A.tl = W.d_tl;
 #endif
-  const size_t lds = 4 * (kN + kLook) + 4 * (kDocLds + 4) + 16;  // ~4.8 KB: 7 waves/SIMD fit
   // pools: decisions (int32, shuffled order) and shuffle draws (uint16), sized from the kept
   // tokens (expected use ~0.15 * 1.5 and ~1.5 times dup * tokens); a plan that outgrows them
   // reports the exact sizes and is planned again (deterministic replay)
-  unsigned long long* pool_ctl;  // [0] masks used, [1] overflow flag, [2] draws used, [3] max pairs
-  if ((rc = W.tmp.take(&pool_ctl, 4)) || (rc = P->mem.take(&P->part_base, n_part + 1))) return rc;
-  int64_t cap = 0, jcap = 0;
-  const int jbytes = prm->seq <= 256 ? 1 : 2;  // every draw j_i < nc <= seq - 3
+  if ((rc = W.tmp.take(&W.pool_ctl, 4)) || (rc = P->mem.take(&P->part_base, n_part + 1))) return rc;
+  W.cap = W.jcap = 0;
+  A.jbytes = prm->seq <= 256 ? 1 : 2;  // every draw j_i < nc <= seq - 3
   if (prm->masking && W.n_sent) {
-    cap = (int64_t)(2.0 * prm->masked_lm_ratio * prm->dup * (double)W.n_kept_tok) +
-          (int64_t)prm->dup * P->n_kept_sent / 2 + kPoolChunk * (n_part + 16);
-    jcap = (int64_t)(1.6 * prm->dup * (double)W.n_kept_tok) + 8 * slots +
-           kPoolChunk * (n_part + 16);  // + the 16-entry alignment of every pair's draws
-    if (const char* e = getenv("LDDL_AMD_MASK_POOL")) cap = atoll(e);  // tests: force a re-plan
+    W.cap = (int64_t)(2.0 * prm->masked_lm_ratio * prm->dup * (double)W.n_kept_tok) +
+            (int64_t)prm->dup * P->n_kept_sent / 2 + kPoolChunk * (n_part + 16);
+    W.jcap = (int64_t)(1.6 * prm->dup * (double)W.n_kept_tok) + 8 * slots +
+             kPoolChunk * (n_part + 16);  // + the 16-entry alignment of every pair's draws
+    if (const char* e = getenv("LDDL_AMD_MASK_POOL")) W.cap = atoll(e);  // tests: force a re-plan
   }
   // SlotPool keeps pool offsets as 32-bit multiples of 8 / 16 entries
-  if (cap / 8 >= (int64_t)UINT32_MAX || jcap / 16 >= (int64_t)UINT32_MAX)
+  if (W.cap / 8 >= (int64_t)UINT32_MAX || W.jcap / 16 >= (int64_t)UINT32_MAX)
     LDDL_FAIL(-1, "batch too large for the mask pools (split it into smaller GPU batches)");
-  for (int attempt = 0; n_part; ++attempt) {
-    int32_t* mtok = nullptr;
-    uint8_t* jpool = nullptr;
-    if (prm->masking) {
-      LDDL_HIP(hipMemsetAsync(pool_ctl, 0, 32, st));
-      if ((rc = P->mem.take(&mtok, cap + 4)) || (rc = W.tmp.take(&jpool, jbytes * (jcap + 16))))
-        return rc;
-    }
-    A.mtok = mtok;
-    A.jpool = jpool;
-    A.jbytes = jbytes;
-    A.pool_cap = cap;
-    A.jpool_cap = jcap;
-    A.pool_used = pool_ctl;
-    A.overflow = reinterpret_cast<int32_t*>(pool_ctl + 1);
+  A.pool_used = W.pool_ctl;
+  A.overflow = reinterpret_cast<int32_t*>(W.pool_ctl + 1);
+  return 0;
+}
+
+typedef void (*PlanKernel)(PlanArgs);
+static PlanKernel planner_kernel(const PlanWork& W) {
+  const bool docs_lds = W.max_docs + 1 <= (unsigned long long)kDocLds;  // document table in LDS
+  return docs_lds ? (W.A.jbytes == 1 ? plan_replay_kernel<true, 1> : plan_replay_kernel<true, 2>)
+                  : (W.A.jbytes == 1 ? plan_replay_kernel<false, 1> : plan_replay_kernel<false, 2>);
+}
+constexpr size_t kPlanLds = 4 * (kN + kLook) + 4 * (kDocLds + 4) + 16;  // ~4.8 KB: 7 waves/SIMD fit
+
+// The head range of a split replay plan with static masking (0: one range): what the device
+// holds of the planner's one-wave workgroups at once, see plan_split_point.
+static int choose_split(const PlanWork& W, int64_t* s) {
+  *s = 0;
+  if (!W.prm->masking || W.n_part <= 0 || W.split_knob == 0) return 0;
+  int64_t capacity = 0;
+  if (W.split_knob < 0) {
+    int per_cu = 0, n_cu = 0;
+    LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, planner_kernel(W), 64, kPlanLds));
+    LDDL_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, W.c->device));
+    capacity = (int64_t)per_cu * n_cu;
+  }
+  *s = plan_split_point(W.n_part, capacity, W.split_knob);
+  return 0;
+}
+
+// The pools of one planning attempt (the counters cleared on the stream first). A split plan also
+// takes `mpos` here, at the pool's capacity: mpos shares the mask pool's index space, and the
+// head's mask replay fills it while the tail range still allocates from the pool.
+static int take_pools(lddl_pairs* P, PlanWork& W, bool split) {
+  W.mtok_try = nullptr;
+  W.jpool_try = nullptr;
+  int rc;
+  if (W.prm->masking) {
+    LDDL_HIP(hipMemsetAsync(W.pool_ctl, 0, 32, W.st));
+    if ((rc = P->mem.take(&W.mtok_try, W.cap + 4)) ||
+        (rc = W.tmp.take(&W.jpool_try, W.A.jbytes * (W.jcap + 16))))
+      return rc;
+    if (split && (rc = P->mem.take(&P->mpos, W.cap + 4))) return rc;
+  }
+  W.A.mtok = W.mtok_try;
+  W.A.jpool = W.jpool_try;
+  W.A.pool_cap = W.cap;
+  W.A.jpool_cap = W.jcap;
+  return 0;
+}
+
+// One plan_replay_kernel launch over partitions [p0, p0 + n) on `st`. with_dense: its extra
+// workgroups pack the kept sentences from *dense_lo on (null: all of them).
+static int launch_planner(const PlanWork& W, int64_t p0, int64_t n, hipStream_t st, bool with_dense,
+                          const int64_t* dense_lo) {
+  PlanArgs A = W.A;
+  A.p0 = (int32_t)p0;
+  A.n_part = (int32_t)n;
+  A.dense_lo = dense_lo;
+  if (!with_dense) A.n_kept_sent = 0;
+  const unsigned grid = (unsigned)n + (A.n_kept_sent ? (unsigned)A.n_dense_wg : 0u);
+  if (grid) hipLaunchKernelGGL(planner_kernel(W), dim3(grid), dim3(64), kPlanLds, st, A);
+  LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
+// One range: launches plan_replay_kernel (between the plan's two events) and, when a pool
+// overflowed, once more with the exact sizes. attempt 1: the re-plan of a split plan.
+static int plan_replay_unsplit(lddl_pairs* P, PlanWork& W, int attempt) {
+  const lddl_pair_params* prm = W.prm;
+  const int64_t n_part = W.n_part;
+  hipStream_t st = W.st;
+  int rc;
+  for (; n_part; ++attempt) {
+    if ((rc = take_pools(P, W, false))) return rc;
     LDDL_HIP(hipEventRecord(P->ev[0], st));
-    const dim3 grid((unsigned)n_part + (A.n_kept_sent ? (unsigned)A.n_dense_wg : 0u));
-    const bool docs_lds = W.max_docs + 1 <= (unsigned long long)kDocLds;  // document table in LDS
-    auto kern = docs_lds ? (jbytes == 1 ? plan_replay_kernel<true, 1> : plan_replay_kernel<true, 2>)
-                         : (jbytes == 1 ? plan_replay_kernel<false, 1> : plan_replay_kernel<false, 2>);
-    hipLaunchKernelGGL(kern, grid, dim3(64), lds, st, A);
-    LDDL_HIP(hipGetLastError());
+    if ((rc = launch_planner(W, 0, n_part, st, true, nullptr))) return rc;
     LDDL_HIP(hipEventRecord(P->ev[1], st));
     // pairs per partition -> output offsets and the largest count, read back with the pool
     // counters in the planner's one sync
-    if (!prm->masking) LDDL_HIP(hipMemsetAsync(pool_ctl, 0, 32, st));
+    if (!prm->masking) LDDL_HIP(hipMemsetAsync(W.pool_ctl, 0, 32, st));
     LDDL_HIP(scan_exclusive(Identity{W.part_npairs}, n_part, P->part_base, W.scratch, st));
-    hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs, n_part, pool_ctl + 3);
+    hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs, n_part, W.pool_ctl + 3);
     unsigned long long ctl[4];
-    LDDL_HIP(hipMemcpyAsync(ctl, pool_ctl, 32, hipMemcpyDeviceToHost, st));
+    LDDL_HIP(hipMemcpyAsync(ctl, W.pool_ctl, 32, hipMemcpyDeviceToHost, st));
     LDDL_HIP(hipMemcpyAsync(&P->n_pairs, P->part_base + n_part, 8, hipMemcpyDeviceToHost, st));
     LDDL_HIP(hipStreamSynchronize(st));
     W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
     if (!prm->masking) break;
     if (!ctl[1]) {
-      P->mtok = mtok;
-      W.jpool = jpool;
+      P->mtok = W.mtok_try;
+      W.jpool = W.jpool_try;
       if ((rc = P->mem.take(&P->mpos, (int64_t)ctl[0]))) return rc;
       break;
     }
-    P->mem.give(mtok);
-    W.tmp.give(jpool);
+    P->mem.give(W.mtok_try);
+    W.tmp.give(W.jpool_try);
     if (attempt > 0) LDDL_FAIL(-1, "mask pool overflow after resize");
-    cap = (int64_t)ctl[0] + 1024;
-    jcap = (int64_t)ctl[2] + 1024;
+    W.cap = (int64_t)ctl[0] + 1024;
+    W.jcap = (int64_t)ctl[2] + 1024;
   }
   return 0;
 }
 
-// random.shuffle(partition_pairs), alone on the stream (its blocks need 16 waves and ~90 KB of
-// LDS per CU: beside fy_resolve's small blocks on a second stream they waited for CUs to
-// drain, 10.3 ms against ~2 alone); its last pass writes the pair maps (see PairMaps): with
+// The context's side stream for the tail range: non-blocking (the caller's stream may be the
+// null stream) and of the lowest priority, so the head range's workgroups are placed first.
+static int plan_side_stream(lddl_ctx* c, hipStream_t* out) {
+  if (!c->plan_side) {
+    int least = 0, greatest = 0;
+    LDDL_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    LDDL_HIP(hipStreamCreateWithPriority(&c->plan_side, hipStreamNonBlocking, least));
+  }
+  *out = c->plan_side;
+  return 0;
+}
+
+// Split plan, first half: the head range [0, s) on the caller's stream and the tail range
+// [s, n_part) on the side stream, both allocating from the same pools. The tail launch keeps the
+// dense-packing workgroups for its kept sentences; the head's are packed by densify_head_kernel,
+// first on the caller's stream after the head planner (by then every tail workgroup that fits is
+// resident). Returns after the head's sync with rg[0].n_pairs and *usable = no pool overflow so
+// far (else the head's slots may point past the pools and nothing downstream may run on them).
+static int plan_replay_split_head(lddl_pairs* P, PlanWork& W, bool* usable) {
+  const int64_t n_part = W.n_part, s = W.split;
+  hipStream_t st = W.st, side;
+  int rc;
+  if ((rc = plan_side_stream(W.c, &side)) || (rc = take_pools(P, W, true)) ||
+      (rc = W.tmp.take(&W.split_info, 2)) || (rc = W.tmp.take(&W.tail_rel, n_part - s + 1)))
+    return rc;
+  LDDL_HIP(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming));
+  LDDL_HIP(hipEventCreateWithFlags(&P->ev_join, hipEventDisableTiming));
+  hipLaunchKernelGGL(split_info_kernel, dim3(1), dim3(1), 0, st, P->kp_off, P->kd_off, P->kscan, s,
+                     W.split_info);
+  LDDL_HIP(hipGetLastError());
+  LDDL_HIP(hipEventRecord(P->ev[0], st));
+  // the side stream starts after the compaction (and everything else queued on st so far)
+  LDDL_HIP(hipEventRecord(P->ev_fork, st));
+  LDDL_HIP(hipStreamWaitEvent(side, P->ev_fork, 0));
+  if ((rc = launch_planner(W, 0, s, st, false, nullptr))) return rc;
+  P->tail_pending = true;  // (from here every return path joins before a block goes back)
+  rc = launch_planner(W, s, n_part - s, side, true, W.split_info);
+  LDDL_HIP(hipEventRecord(P->ev_join, side));
+  if (rc) return rc;
+  if (P->n_kept_sent)
+    hipLaunchKernelGGL(densify_head_kernel, dim3((unsigned)((P->n_kept_sent + 255) / 256)), dim3(256),
+                       0, st, P->ks_start, P->ks_len, P->kscan, W.split_info, W.d_ids, P->dense);
+  LDDL_HIP(scan_exclusive(Identity{W.part_npairs}, s, P->part_base, W.scratch, st));
+  hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs, s, W.pool_ctl + 3);
+  LDDL_HIP(hipGetLastError());
+  unsigned long long ctl[4];
+  LDDL_HIP(hipMemcpyAsync(ctl, W.pool_ctl, 32, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipMemcpyAsync(&P->rg[0].n_pairs, P->part_base + s, 8, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipMemcpyAsync(W.h_split_info, W.split_info, 16, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipStreamSynchronize(st));
+  W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
+  *usable = ctl[1] == 0;
+  return 0;
+}
+
+// random.shuffle(partition_pairs) of one range, alone on the stream (its blocks need 16 waves
+// and ~90 KB of LDS per CU: beside fy_resolve's small blocks on a second stream they waited for
+// CUs to drain, 10.3 ms against ~2 alone); its last pass writes the pair maps (see PairMaps): with
 // masking the planner-order slots and their output positions (the mask replay writes each
-// pair's gather record there), else the output order
-static int shuffle_partitions(lddl_pairs* P, PlanWork& W) {
+// pair's gather record there), else the output order. rel_base[i]: the first pair of the
+// range's partition i, counted from the range's first pair.
+static int shuffle_partitions(lddl_pairs* P, PlanWork& W, const PairRange& r, const int64_t* rel_base) {
   const lddl_pair_params* prm = W.prm;
-  const int64_t n_part = W.n_part;
+  const int64_t n_part = r.p1 - r.p0;
   hipStream_t st = W.st;
   int rc;
   PairMaps& M = W.M;
-  M.part_base = P->part_base;
+  M = PairMaps{rel_base, nullptr, nullptr, nullptr};
   if (prm->masking) {
-    if ((rc = W.tmp.take(&M.slots, P->n_pairs)) || (rc = W.tmp.take(&M.dstq, P->n_pairs))) return rc;
+    if ((rc = W.tmp.take(&M.slots, r.n_pairs)) || (rc = W.tmp.take(&M.dstq, r.n_pairs))) return rc;
   } else {
-    if ((rc = P->mem.take(&P->src, P->n_pairs))) return rc;
+    if ((rc = P->mem.take(&P->src, r.n_pairs))) return rc;
     M.src = P->src;
   }
   if (n_part) {
     const int64_t cap = W.max_np;
+    const int64_t* kp_off = P->kp_off + r.p0;  // (the kernels index partitions by workgroup)
+    const int64_t* part_npairs = W.part_npairs + r.p0;
     // dynamic-LDS budget of the swap kernel: what the device grants a block (160 KiB on
     // gfx950), minus headroom for the kernel's static LDS
     const size_t kLdsBudget = std::min<size_t>(150 * 1024, W.c->lds_per_block > 10 * 1024
@@ -2700,13 +2916,13 @@ static int shuffle_partitions(lddl_pairs* P, PlanWork& W) {
     const int64_t cap_lds = force_global ? 0 : std::min<int64_t>({cap, 65534, (int64_t)(kLdsBudget / 6) - 2});
     if (cap_lds > 0)
       hipLaunchKernelGGL(shuffle_sort_kernel, dim3((unsigned)n_part), dim3(kShufThreads),
-                         (size_t)6 * (size_t)((cap_lds + 2) & ~1), st, P->kd_off, P->kp_off,
-                         prm->dup, W.part_npairs, W.jseq, P->order, (int32_t)cap_lds, M);
+                         (size_t)6 * (size_t)((cap_lds + 2) & ~1), st, P->kd_off, kp_off,
+                         prm->dup, part_npairs, W.jseq, P->order, (int32_t)cap_lds, M);
     if (cap > cap_lds) {  // partitions beyond the LDS tables: swaps in global memory, then the maps
       hipLaunchKernelGGL(apply_shuffle_kernel, dim3((unsigned)n_part), dim3(64), 0, st, P->kd_off,
-                         P->kp_off, prm->dup, W.part_npairs, W.jseq, P->order, cap_lds);
+                         kp_off, prm->dup, part_npairs, W.jseq, P->order, cap_lds);
       hipLaunchKernelGGL(map_pairs_kernel, dim3((unsigned)n_part), dim3(256), 0, st, P->kd_off,
-                         P->kp_off, prm->dup, M.part_base, (const int32_t*)P->order, M.src, M.slots,
+                         kp_off, prm->dup, M.part_base, (const int32_t*)P->order, M.src, M.slots,
                          M.dstq);
     }
   }
@@ -2772,13 +2988,13 @@ static int report_plan_stamps(const PlanWork& W) {
 
 // The mask replay (fy_resolve, planner order): every pair's mask positions, and its gather
 // record and counts at its output position.
-static int resolve_masks(lddl_pairs* P, PlanWork& W) {
-  if (!P->n_pairs) return 0;
+static int resolve_masks(lddl_pairs* P, PlanWork& W, const PairRange& r) {
+  if (!r.n_pairs) return 0;
   const int32_t seq = P->seq;
   const FyKnobs& fy = W.fy;
   hipStream_t st = W.st;
-  ResolveArgs RA{W.M.slots, P->n_pairs, P->desc, W.spool, W.jpool, P->mpos, P->kscan, P->dense,
-                 P->cls_id, P->sep_id, W.M.dstq, P->rec, W.pcnt, 0};
+  ResolveArgs RA{W.M.slots, r.n_pairs, P->desc, W.spool, W.jpool, P->mpos, P->kscan, P->dense,
+                 P->cls_id, P->sep_id, W.M.dstq, r.rec, W.pcnt, 0};
   // a lane's column covers the padded draw region (steps up to nc rounded up to 16)
   const size_t col = (size_t)((seq + 15) & ~15);
   RA.col_rows = (int32_t)col;
@@ -2791,7 +3007,7 @@ static int resolve_masks(lddl_pairs* P, PlanWork& W) {
   // draw vectors (8 steps each) in flight per lane at seq > 256 (A/B: LDDL_FY_PF=2 / 8)
 #define LDDL_FY_LAUNCH(T, NG, LW, BF, ...)                                                     \
   hipLaunchKernelGGL((fy_resolve_kernel<T, T, NG, LW, BF, ##__VA_ARGS__>),                     \
-                     dim3((unsigned)((P->n_pairs + LW - 1) / LW)), dim3(LW),                   \
+                     dim3((unsigned)((r.n_pairs + LW - 1) / LW)), dim3(LW),                   \
                      (size_t)LW * sizeof(T) * col, st, RA)
   if (seq <= 131) {  // nc <= 128: all draws in registers (8 uint4 of 1-byte draws); 64
     // pairs per wave (C2: 10.2 ms; 32 per wave 11.9, 16 per wave 20.1, profiles/r04slw_*)
@@ -2818,17 +3034,41 @@ static int resolve_masks(lddl_pairs* P, PlanWork& W) {
   return 0;
 }
 
-// Layout of a replay plan (part_base and n_pairs came with the planner's sync). With masking, the
-// mask replay also writes every pair's gather record at its output position and the two
-// output-order scans follow; without, pair_prep builds the records from the output order.
+// Layout of one range of a replay plan with masking (its pair count came with the planner's
+// sync): the mask replay writes every pair's masks, and its gather record and counts at its
+// output position; the two output-order scans follow.
 // (Round 4 ran pair_prep beside fy_resolve on a second stream: 15.6 ms for the section, both
 // kernels slowed by the other; the fused replay reads each slot record once.)
-static int layout_replay(lddl_pairs* P, PlanWork& W) {
-  if (!P->masking) return layout_pairs(P, W);
+static int layout_replay(lddl_pairs* P, PlanWork& W, PairRange& r) {
   int rc;
-  if ((rc = layout_alloc(P, W)) || (rc = resolve_masks(P, W))) return rc;
+  if ((rc = layout_alloc(P, W, r)) || (rc = resolve_masks(P, W, r))) return rc;
   LDDL_HIP(hipGetLastError());
-  return layout_scan(P, W);
+  return layout_scan(P, W, r);
+}
+
+// Everything downstream of the planner for a one-range replay plan. Without masking, pair_prep
+// builds the records from the output order.
+static int finish_unsplit(lddl_pairs* P, PlanWork& W) {
+  int rc;
+  P->n_rg = 1;
+  PairRange& r = P->rg[0];
+  r = PairRange{};
+  r.p1 = W.n_part;
+  r.n_pairs = P->n_pairs;
+  if ((rc = shuffle_partitions(P, W, r, P->part_base))) return rc;
+#ifdef LDDL_STAMPS
+  if ((rc = report_plan_stamps(W))) return rc;
+#endif
+  return P->masking ? layout_replay(P, W, r) : layout_pairs(P, W);
+}
+
+// a range's shuffle and layout temporaries, when the next range (or the re-plan) takes its own
+static void give_range_tmp(PlanWork& W) {
+  for (void* b : {(void*)W.M.slots, (void*)W.M.dstq, (void*)W.pcnt, (void*)W.scr2})
+    if (b) W.tmp.give(b);
+  W.M = PairMaps{nullptr, nullptr, nullptr, nullptr};
+  W.pcnt = nullptr;
+  W.scr2 = nullptr;
 }
 
 static int32_t max_predictions(const lddl_pair_params* prm) {
@@ -2837,20 +3077,135 @@ static int32_t max_predictions(const lddl_pair_params* prm) {
   return std::min(std::max(m, 1), prm->seq);
 }
 
-extern "C" int lddl_pairs_plan(lddl_ctx* c, void* stream, const lddl_pair_params* prm,
-                               const int64_t* d_sent_off, const int32_t* d_ids,
-                               const int32_t* d_sent_len, int64_t n_sent,
-                               const int64_t* d_doc_sent_off, int64_t n_doc,
-                               const int64_t* d_part_doc_off, const int64_t* d_part_seed,
-                               int64_t n_part, lddl_pairs** out, int64_t* counts) {
-  *out = nullptr;
-  FyKnobs fy;
+// First half of a plan: the whole plan when it is not split (native RNG, no masking, too few
+// partitions); else the head range planned, resolved and laid out while the tail range's
+// planner still runs on the side stream (P->work carries the call over to plan_tail_stage).
+static int plan_head_stage(lddl_pairs* P, const int64_t* d_sent_off, const int32_t* d_sent_len,
+                           const int64_t* d_doc_sent_off, int64_t n_doc,
+                           const int64_t* d_part_doc_off) {
+  PlanWork& W = *P->work;
   int rc;
-  if ((rc = check_plan_args(c, prm, &fy))) return rc;
+  if ((rc = compact_inputs(P, W, d_sent_off, d_sent_len, d_doc_sent_off, n_doc, d_part_doc_off)))
+    return rc;
+  if (W.prm->rng == LDDL_RNG_NATIVE) {
+    if ((rc = plan_native(P, W))) return rc;
+  } else {
+    if ((rc = plan_replay_setup(P, W)) || (rc = choose_split(W, &W.split))) return rc;
+    if (!W.split) {
+      if ((rc = plan_replay_unsplit(P, W, 0)) || (rc = finish_unsplit(P, W))) return rc;
+    } else {
+      bool usable = false;
+      if ((rc = plan_replay_split_head(P, W, &usable))) return rc;
+      PairRange& r = P->rg[0];
+      r.p1 = W.split;
+      if (usable) {
+        // (the pools of this attempt stand unless the tail overflows them)
+        W.jpool = W.jpool_try;
+        P->mtok = W.mtok_try;
+        if ((rc = shuffle_partitions(P, W, r, P->part_base)) || (rc = layout_replay(P, W, r))) return rc;
+        P->head_valid = true;
+      } else {
+        r.n_pairs = 0;
+      }
+    }
+  }
+  LDDL_HIP(hipStreamSynchronize(W.st));  // the ranges' totals (layout_scan)
+  if (!W.split) {
+    P->n_tokens = P->rg[0].n_tokens;
+    P->n_masked = P->rg[0].n_masked;
+    P->work.reset();
+  }
+  return 0;
+}
+
+// Second half of a split plan: joins the tail range, then either lays it out behind the head
+// (offsets carried in as the range's bases) or, when a pool overflowed, drops the head's tables
+// and plans everything again in one range with the exact pool sizes.
+static int plan_tail_stage(lddl_pairs* P) {
+  if (!P->work) return 0;
+  PlanWork& W = *P->work;
+  hipStream_t st = W.st;
+  const int64_t s = W.split, n_tail = W.n_part - s;
+  int rc;
+  P->join(st);
+  LDDL_HIP(hipEventRecord(P->ev[1], st));
+  LDDL_HIP(scan_exclusive(Identity{W.part_npairs + s}, n_tail, W.tail_rel, W.scratch, st));
+  hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs + s, n_tail,
+                     W.pool_ctl + 3);
+  LDDL_HIP(hipGetLastError());
+  unsigned long long ctl[4];
+  PairRange &h = P->rg[0], &t = P->rg[1];
+  LDDL_HIP(hipMemcpyAsync(ctl, W.pool_ctl, 32, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipMemcpyAsync(&t.n_pairs, W.tail_rel + n_tail, 8, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipStreamSynchronize(st));
+  W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
+  if (ctl[1]) {  // a pool overflowed: the head's output is void; one range, exact sizes
+    P->head_valid = false;
+    give_range_tmp(W);
+    for (void* b : {(void*)W.mtok_try, (void*)P->mpos, (void*)h.rec, (void*)h.tok_off, (void*)h.pos_off})
+      if (b) P->mem.give(b);
+    W.tmp.give(W.jpool_try);
+    P->mtok = nullptr;
+    P->mpos = nullptr;
+    W.jpool = nullptr;
+    h = PairRange{};
+    t = PairRange{};
+    W.split = 0;
+    W.cap = (int64_t)ctl[0] + 1024;
+    W.jcap = (int64_t)ctl[2] + 1024;
+    if ((rc = plan_replay_unsplit(P, W, 1)) || (rc = finish_unsplit(P, W))) return rc;
+    LDDL_HIP(hipStreamSynchronize(st));
+    P->n_tokens = h.n_tokens;
+    P->n_masked = h.n_masked;
+  } else {
+    give_range_tmp(W);
+    if (n_tail)
+      hipLaunchKernelGGL(tail_part_base_kernel, dim3((unsigned)((n_tail + 255) / 256)), dim3(256), 0,
+                         st, W.tail_rel, n_tail, h.n_pairs, P->part_base + s);
+    LDDL_HIP(hipGetLastError());
+    t.p0 = s;
+    t.p1 = W.n_part;
+    t.pair0 = h.n_pairs;
+    t.tok0 = h.n_tokens;
+    t.pos0 = h.n_masked;
+    P->n_rg = 2;
+    if ((rc = shuffle_partitions(P, W, t, W.tail_rel)) || (rc = layout_replay(P, W, t))) return rc;
+    LDDL_HIP(hipStreamSynchronize(st));
+    P->n_pairs = h.n_pairs + t.n_pairs;
+    P->n_tokens = h.n_tokens + t.n_tokens;
+    P->n_masked = h.n_masked + t.n_masked;
+  }
+  P->work.reset();
+  return 0;
+}
+
+static void plan_counts(const lddl_pairs* P, int64_t* counts) {
+  if (!counts) return;
+  counts[0] = P->n_pairs;
+  counts[1] = P->n_tokens;
+  counts[2] = P->n_masked;
+  counts[3] = P->n_kept_sent;
+  counts[4] = P->n_kept_doc;
+}
+
+extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_params* prm,
+                                    const int64_t* d_sent_off, const int32_t* d_ids,
+                                    const int32_t* d_sent_len, int64_t n_sent,
+                                    const int64_t* d_doc_sent_off, int64_t n_doc,
+                                    const int64_t* d_part_doc_off, const int64_t* d_part_seed,
+                                    int64_t n_part, lddl_pairs** out, int64_t* head) {
+  if (out) *out = nullptr;
+  FyKnobs fy;
+  int64_t split_knob;
+  int rc;
+  if (!out) LDDL_FAIL(-1, "null argument");
+  if ((rc = check_plan_args(c, prm, &fy, &split_knob))) return rc;
   hipStream_t st = as_stream(stream);
-  // until it is handed out, an error return drops the plan: its blocks go back on `st`
+  // until it is handed out, an error return drops the plan: its blocks go back on `st` (after
+  // the tail launch, when one is in flight)
   std::unique_ptr<lddl_pairs> P(new lddl_pairs(&c->arena, st));
   P->n_part = n_part;
+  P->prm = *prm;
   P->masking = prm->masking;
   P->seq = prm->seq;
   P->cls_id = c->tab.special_id[kCls];
@@ -2858,30 +3213,101 @@ extern "C" int lddl_pairs_plan(lddl_ctx* c, void* stream, const lddl_pair_params
   P->max_pred = max_predictions(prm);
   LDDL_HIP(hipEventCreate(&P->ev[0]));
   LDDL_HIP(hipEventCreate(&P->ev[1]));
-  PlanWork W{c, prm, d_ids, d_part_seed, n_sent, n_part, st, P->mem, fy};
-  if ((rc = compact_inputs(P.get(), W, d_sent_off, d_sent_len, d_doc_sent_off, n_doc, d_part_doc_off)))
+  P->work.reset(new PlanWork{c, &P->prm, d_ids, d_part_seed, n_sent, n_part, st, P->mem, fy, split_knob});
+  if ((rc = plan_head_stage(P.get(), d_sent_off, d_sent_len, d_doc_sent_off, n_doc, d_part_doc_off)))
     return rc;
-  if (prm->rng == LDDL_RNG_NATIVE) {
-    if ((rc = plan_native(P.get(), W))) return rc;
-  } else {
-    if ((rc = plan_replay(P.get(), W)) || (rc = shuffle_partitions(P.get(), W))) return rc;
-#ifdef LDDL_STAMPS
-    if ((rc = report_plan_stamps(W))) return rc;
-#endif
-    if ((rc = layout_replay(P.get(), W))) return rc;
-  }
-  LDDL_HIP(hipMemcpyAsync(&P->n_tokens, P->tok_off + P->n_pairs, 8, hipMemcpyDeviceToHost, st));
-  if (prm->masking)
-    LDDL_HIP(hipMemcpyAsync(&P->n_masked, P->pos_off + P->n_pairs, 8, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipStreamSynchronize(st));
-  if (counts) {
-    counts[0] = P->n_pairs;
-    counts[1] = P->n_tokens;
-    counts[2] = P->n_masked;
-    counts[3] = P->n_kept_sent;
-    counts[4] = P->n_kept_doc;
+  if (head) {
+    for (int i = 0; i < 8; ++i) head[i] = 0;
+    if (P->work) {  // split: the head's counts and what they predict for the whole plan
+      const PlanWork& W = *P->work;
+      const PairRange& h = P->rg[0];
+      head[0] = 1;
+      head[1] = h.n_pairs;
+      head[2] = h.n_tokens;
+      head[3] = h.n_masked;
+      head[4] = plan_suggest_capacity(h.n_pairs, W.n_kept_tok, W.h_split_info[1]);
+      head[5] = plan_suggest_capacity(h.n_tokens, W.n_kept_tok, W.h_split_info[1]);
+      head[6] = plan_suggest_capacity(h.n_masked, W.n_kept_tok, W.h_split_info[1]);
+    }
   }
   *out = P.release();
+  return 0;
+}
+
+extern "C" int lddl_pairs_plan_tail(lddl_pairs* P, int64_t* counts, int32_t* head_valid) {
+  if (!P) LDDL_FAIL(-1, "null plan");
+  int rc;
+  if ((rc = plan_tail_stage(P))) return rc;
+  plan_counts(P, counts);
+  if (head_valid) *head_valid = P->head_valid ? 1 : 0;
+  return 0;
+}
+
+extern "C" int lddl_pairs_plan(lddl_ctx* c, void* stream, const lddl_pair_params* prm,
+                               const int64_t* d_sent_off, const int32_t* d_ids,
+                               const int32_t* d_sent_len, int64_t n_sent,
+                               const int64_t* d_doc_sent_off, int64_t n_doc,
+                               const int64_t* d_part_doc_off, const int64_t* d_part_seed,
+                               int64_t n_part, lddl_pairs** out, int64_t* counts) {
+  lddl_pairs* P = nullptr;
+  int rc;
+  if (out) *out = nullptr;
+  if ((rc = lddl_pairs_plan_head(c, stream, prm, d_sent_off, d_ids, d_sent_len, n_sent, d_doc_sent_off,
+                                 n_doc, d_part_doc_off, d_part_seed, n_part, &P, nullptr)))
+    return rc;
+  if ((rc = lddl_pairs_plan_tail(P, counts, nullptr))) {
+    delete P;  // (joins, then its blocks go back on the planning stream)
+    return rc;
+  }
+  *out = P;
+  return 0;
+}
+
+// Gathers the plan's ranges [r0, r1) into the caller's buffers (whole-plan indexing).
+static int emit_ranges(lddl_pairs* P, int r0, int r1, void* stream, void* d_tokens, int64_t* d_tok_off,
+                       int32_t* d_len_a, uint8_t* d_is_rn, uint16_t* d_pos, void* d_lab,
+                       int64_t* d_pos_off) {
+  hipStream_t st = as_stream(stream);
+  for (int ri = r0; ri < r1; ++ri) {
+    const PairRange& r = P->rg[ri];
+    if (r.n_pairs == 0) continue;
+    GatherArgs G{};
+    G.dense = P->dense.p;
+    G.rec = r.rec;
+    G.mpos = P->mpos;
+    G.mtok = P->mtok;
+    G.masking = P->masking;
+    G.n_pairs = r.n_pairs;
+    G.tok_off = r.tok_off;
+    G.pos_off = r.pos_off;
+    G.tok_base = r.tok0;
+    G.pos_base = r.pos0;
+    G.out_tok = d_tokens;
+    G.len_a = d_len_a + r.pair0;
+    G.is_rn = d_is_rn + r.pair0;
+    G.out_pos = d_pos;
+    G.out_lab = d_lab;
+    G.out_tok_off = d_tok_off ? d_tok_off + r.pair0 : nullptr;
+    G.out_pos_off = d_pos_off ? d_pos_off + r.pair0 : nullptr;
+    GatherLds Lg{(P->seq + 127) / 128 * 128, P->dense.ib, P->dense.ib == 2 && P->seq <= 600 ? 2 : 4};
+    auto launch = [&](auto kern, int K) {
+      const int64_t per_wg = (int64_t)2 * K * kGWaves;
+      const int64_t nwg = (r.n_pairs + per_wg - 1) / per_wg;
+      const int64_t gx = std::min<int64_t>(nwg, 65536);
+      const size_t lds = P->masking ? (size_t)kGWaves * 2 * K * Lg.per_pair() : 0;
+      hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)((nwg + gx - 1) / gx)), dim3(64 * kGWaves),
+                         lds, st, G, Lg);
+    };
+    const bool i16 = P->dense.ib == 2;
+    if (P->seq <= 600) {
+      if (i16) launch(gather16_kernel<16>, 2);  // (4 pairs per wave, like K = 2; LP = 8: 35.3 ms, r04ze)
+      else launch(gather_kernel<2, int32_t>, 2);
+    } else {  // (LDS: seq-entry decision tables)
+      if (i16) launch(gather_kernel<1, uint16_t>, 1);
+      else launch(gather_kernel<1, int32_t>, 1);
+    }
+    LDDL_HIP(hipGetLastError());
+  }
   return 0;
 }
 
@@ -2889,47 +3315,32 @@ extern "C" int lddl_pairs_emit(lddl_pairs* P, void* stream, void* d_tokens, int6
                                int32_t* d_len_a, uint8_t* d_is_rn, uint16_t* d_pos, void* d_lab,
                                int64_t* d_pos_off) {
   if (!P) LDDL_FAIL(-1, "null plan");
-  hipStream_t st = as_stream(stream);
-  if (P->n_pairs == 0) return 0;
-  GatherArgs G{};
-  G.dense = P->dense.p;
-  G.rec = P->rec;
-  G.mpos = P->mpos;
-  G.mtok = P->mtok;
-  G.masking = P->masking;
-  G.n_pairs = P->n_pairs;
-  G.tok_off = P->tok_off;
-  G.pos_off = P->pos_off;
-  G.out_tok = d_tokens;
-  G.len_a = d_len_a;
-  G.is_rn = d_is_rn;
-  G.out_pos = d_pos;
-  G.out_lab = d_lab;
-  G.out_tok_off = d_tok_off;
-  G.out_pos_off = d_pos_off;
-  GatherLds Lg{(P->seq + 127) / 128 * 128, P->dense.ib, P->dense.ib == 2 && P->seq <= 600 ? 2 : 4};
-  auto launch = [&](auto kern, int K) {
-    const int64_t per_wg = (int64_t)2 * K * kGWaves;
-    const int64_t nwg = (P->n_pairs + per_wg - 1) / per_wg;
-    const int64_t gx = std::min<int64_t>(nwg, 65536);
-    const size_t lds = P->masking ? (size_t)kGWaves * 2 * K * Lg.per_pair() : 0;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)((nwg + gx - 1) / gx)), dim3(64 * kGWaves),
-                       lds, st, G, Lg);
-  };
-  const bool i16 = P->dense.ib == 2;
-  if (P->seq <= 600) {
-    if (i16) launch(gather16_kernel<16>, 2);  // (4 pairs per wave, like K = 2; LP = 8: 35.3 ms, r04ze)
-    else launch(gather_kernel<2, int32_t>, 2);
-  } else {  // (LDS: seq-entry decision tables)
-    if (i16) launch(gather_kernel<1, uint16_t>, 1);
-    else launch(gather_kernel<1, int32_t>, 1);
-  }
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  if (P->work) LDDL_FAIL(-1, "lddl_pairs_emit before lddl_pairs_plan_tail");
+  return emit_ranges(P, 0, P->n_rg, stream, d_tokens, d_tok_off, d_len_a, d_is_rn, d_pos, d_lab,
+                     d_pos_off);
+}
+
+extern "C" int lddl_pairs_emit_head(lddl_pairs* P, void* stream, void* d_tokens, int64_t* d_tok_off,
+                                    int32_t* d_len_a, uint8_t* d_is_rn, uint16_t* d_pos, void* d_lab,
+                                    int64_t* d_pos_off) {
+  if (!P) LDDL_FAIL(-1, "null plan");
+  if (!P->work) LDDL_FAIL(-1, "lddl_pairs_emit_head: not a split plan between its head and tail calls");
+  if (!P->head_valid) return 0;  // (a pool overflowed: lddl_pairs_plan_tail will say so)
+  return emit_ranges(P, 0, 1, stream, d_tokens, d_tok_off, d_len_a, d_is_rn, d_pos, d_lab, d_pos_off);
+}
+
+extern "C" int lddl_pairs_emit_tail(lddl_pairs* P, void* stream, void* d_tokens, int64_t* d_tok_off,
+                                    int32_t* d_len_a, uint8_t* d_is_rn, uint16_t* d_pos, void* d_lab,
+                                    int64_t* d_pos_off) {
+  if (!P) LDDL_FAIL(-1, "null plan");
+  if (P->work || P->n_rg != 2 || !P->head_valid)
+    LDDL_FAIL(-1, "lddl_pairs_emit_tail: no valid head range (use lddl_pairs_emit)");
+  return emit_ranges(P, 1, 2, stream, d_tokens, d_tok_off, d_len_a, d_is_rn, d_pos, d_lab, d_pos_off);
 }
 
 extern "C" int lddl_pairs_destroy(lddl_pairs* P, void* stream) {
   if (!P) return 0;
+  P->join(as_stream(stream));  // (a split plan dropped before its tail call)
   P->mem.release(as_stream(stream));  // (the last use of the blocks was on this stream)
   delete P;
   return 0;

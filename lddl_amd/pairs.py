@@ -3,6 +3,7 @@
 (lddl/dask/bert/pretrain.py:386-402, 241-365, 182-238).
 """
 import ctypes
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -62,12 +63,49 @@ class PairBatch:
         return out
 
 
+def _alloc_outputs(ctx, dev, masking, n_pairs, n_tok, n_mask):
+    """Output buffers of the gather for the given capacities (views of at least one element)."""
+    out = dict(tokens=torch.empty(max(n_tok, 1), dtype=ctx.id_dtype, device=dev),
+               tok_off=torch.empty(n_pairs + 1, dtype=torch.int64, device=dev),
+               len_a=torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev),
+               is_rn=torch.empty(max(n_pairs, 1), dtype=torch.uint8, device=dev),
+               pos=None, labels=None, pos_off=None)
+    if masking:
+        out.update(pos=torch.empty(max(n_mask, 1), dtype=torch.int16, device=dev),
+                   labels=torch.empty(max(n_mask, 1), dtype=ctx.id_dtype, device=dev),
+                   pos_off=torch.empty(n_pairs + 1, dtype=torch.int64, device=dev))
+    return out
+
+
+_OUT_KEYS = ('tokens', 'tok_off', 'len_a', 'is_rn', 'pos', 'labels', 'pos_off')
+
+
+def _emit_args(o):
+    return [_ptr(o[k]) for k in _OUT_KEYS]
+
+
+def _head_gather():
+    """A/B knob LDDL_PLAN_HEAD_GATHER: 1 (default) gathers a split plan's head range before its
+    tail range is planned, 0 gathers everything after the plan (the head's resolve and layout
+    still run under the tail)."""
+    v = os.environ.get('LDDL_PLAN_HEAD_GATHER', '1')
+    if v not in ('0', '1'):
+        raise ValueError('LDDL_PLAN_HEAD_GATHER must be 0 or 1')
+    return v == '1'
+
+
 def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_seed, seq=128,
                dup=5, masking=False, short_seq_prob=0.1, masked_lm_ratio=0.15, rng='replay',
-               native_seed=12345):
+               native_seed=12345, _capacity_scale=1.0, _trace=None):
     """All inputs are cuda tensors (int64 offsets / seeds; tokenizer output from Context.tokenize).
 
     rng='replay' reproduces CPython `random` after random.seed(part_seed[p]) per partition.
+
+    A large replay batch with static masking is planned in two partition ranges
+    (include/lddl_amd.h, lddl_pairs_plan_head): the first range's pairs are gathered, into
+    buffers sized from its counts, while the planner still works on the second.
+    (_capacity_scale: tests only, scales those sizes to force the regrow path; _trace: a dict
+    that receives which path ran.)
     """
     dev = ctx.device
     prm = PairParams(seq, dup, int(bool(masking)), RNG_REPLAY if rng == 'replay' else RNG_NATIVE,
@@ -77,29 +115,55 @@ def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_se
     n_part = part_doc_off.numel() - 1
     h = ctypes.c_void_p()
     counts = np.zeros(5, np.int64)
+    head = np.zeros(8, np.int64)
+    head_valid = ctypes.c_int32(0)
     st = _stream()
-    check(lib.lddl_pairs_plan(ctx.handle, st, ctypes.byref(prm), _ptr(sent_off), _ptr(ids),
-                              _ptr(sent_len), n_sent, _ptr(doc_sent_off), n_doc, _ptr(part_doc_off),
-                              _ptr(part_seed), n_part, ctypes.byref(h), counts.ctypes.data))
+    check(lib.lddl_pairs_plan_head(ctx.handle, st, ctypes.byref(prm), _ptr(sent_off), _ptr(ids),
+                                   _ptr(sent_len), n_sent, _ptr(doc_sent_off), n_doc,
+                                   _ptr(part_doc_off), _ptr(part_seed), n_part, ctypes.byref(h),
+                                   head.ctypes.data))
     try:
+        o = None
+        caps = (0, 0, 0)
+        if head[0] and _head_gather():  # split: gather the head range under the tail's planner
+            caps = tuple(max(int(head[1 + i]), int(int(head[4 + i]) * _capacity_scale))
+                         for i in range(3))
+            o = _alloc_outputs(ctx, dev, masking, *caps)
+            check(lib.lddl_pairs_emit_head(h, st, *_emit_args(o)))
+        check(lib.lddl_pairs_plan_tail(h, counts.ctypes.data, ctypes.byref(head_valid)))
         n_pairs, n_tok, n_mask = int(counts[0]), int(counts[1]), int(counts[2])
-        tokens = torch.empty(max(n_tok, 1), dtype=ctx.id_dtype, device=dev)[:n_tok]
-        tok_off = torch.empty(n_pairs + 1, dtype=torch.int64, device=dev)
-        len_a = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-        is_rn = torch.empty(n_pairs, dtype=torch.uint8, device=dev)
-        pos = labels = pos_off = None
-        if masking:
-            pos = torch.empty(max(n_mask, 1), dtype=torch.int16, device=dev)[:n_mask]
-            labels = torch.empty(max(n_mask, 1), dtype=ctx.id_dtype, device=dev)[:n_mask]
-            pos_off = torch.empty(n_pairs + 1, dtype=torch.int64, device=dev)
-        check(lib.lddl_pairs_emit(h, st, _ptr(tokens), _ptr(tok_off), _ptr(len_a), _ptr(is_rn),
-                                  _ptr(pos), _ptr(labels), _ptr(pos_off)))
+        if o is not None and head_valid.value and all(c >= n for c, n in zip(caps, counts[:3])):
+            check(lib.lddl_pairs_emit_tail(h, st, *_emit_args(o)))
+            path = 'tail'
+        elif o is not None and head_valid.value:  # a capacity is short: exact sizes, head copied
+            big = _alloc_outputs(ctx, dev, masking, n_pairs, n_tok, n_mask)
+            hp, ht, hm = (int(x) for x in head[1:4])
+            for k, n in (('tokens', ht), ('tok_off', hp), ('len_a', hp), ('is_rn', hp), ('pos', hm),
+                         ('labels', hm), ('pos_off', hp)):
+                if big[k] is not None and n:
+                    big[k][:n].copy_(o[k][:n])
+            o = big
+            check(lib.lddl_pairs_emit_tail(h, st, *_emit_args(o)))
+            path = 'copy'
+        else:
+            o = _alloc_outputs(ctx, dev, masking, n_pairs, n_tok, n_mask)
+            check(lib.lddl_pairs_emit(h, st, *_emit_args(o)))
+            path = 'full'
+        if _trace is not None:
+            _trace.update(split=int(head[0]), head_pairs=int(head[1]),
+                          head_valid=int(head_valid.value), path=path)
         part_off = torch.empty(n_part + 1, dtype=torch.int64, device=dev)
         check(lib.lddl_pairs_part_offsets(h, st, _ptr(part_off)))
         ms = ctypes.c_float()
         check(lib.lddl_pairs_plan_ms(h, ctypes.byref(ms)))
     finally:
         lib.lddl_pairs_destroy(h, st)
+    # exact-length views (a view of a larger buffer when the head's capacities were used)
+    tokens, tok_off = o['tokens'][:n_tok], o['tok_off'][:n_pairs + 1]
+    len_a, is_rn = o['len_a'][:n_pairs], o['is_rn'][:n_pairs]
+    pos = labels = pos_off = None
+    if masking:
+        pos, labels, pos_off = o['pos'][:n_mask], o['labels'][:n_mask], o['pos_off'][:n_pairs + 1]
     return PairBatch(tokens, tok_off, len_a, is_rn, pos, labels, pos_off, int(counts[3]),
                      int(counts[4]), part_off, float(ms.value), n_mask)
 
