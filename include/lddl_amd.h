@@ -455,6 +455,52 @@ int lddl_collate_encode_masked_ww(lddl_ctx* ctx, void* stream, const uint8_t* d_
                                   float mlm_probability, int64_t ignore_index, int64_t vocab_len,
                                   uint64_t seed, uint64_t counter);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sequence-packed collate (past the reference): several samples share one row of
+ * max_seq_length slots. The host plans the rows; per sample i (len = na + nb + 3):
+ *   d_dst[i]         flat slot row * max_seq_length + start of the sample's [CLS]
+ *   d_fill[i]        slots its wave writes: len, plus the row's unused tail if it is the row's
+ *                    last sample. The segments [dst, dst + fill) must tile the [R, L] outputs:
+ *                    every element is then written exactly once (no memset needed)
+ *   d_seq_in_row[i]  1-based index of the sample inside its row
+ * Outputs, all [R, max_seq_length] int64: slot x < len of the segment holds what the unpacked
+ * entry point puts at [i, x], position_ids = x and sequence_ids = seq_in_row; slots
+ * [len, fill) are padding: input_ids, token_type_ids, attention_mask, position_ids and
+ * sequence_ids 0, labels ignore_index, special_tokens_mask 1. A sample with
+ * len > max_seq_length is not written (the host refuses it).
+ *
+ * lddl_collate_seqpack: lddl_collate_encode. Static masking (d_lab_bytes given: positions count
+ * from the sample's [CLS], one >= len is dropped; writes d_labels, d_special_tokens_mask NULL)
+ * or dynamic unmasked (d_lab_bytes NULL: writes d_special_tokens_mask, d_labels NULL).
+ * lddl_collate_seqpack_masked: lddl_collate_encode_masked, or with whole_word != 0
+ * lddl_collate_encode_masked_ww (64-slot windows from the sample's start). The Philox index of
+ * slot x of sample i is i * draw_stride + x: with draw_stride = the seq_len of the unpacked call
+ * and equal seed / counter, the segment is bit-identical to row i of the unpacked output.
+ * Both fail with -1 on a NULL context, a NULL output or plan array, a vocab without [CLS] and
+ * [SEP] (masked: and [MASK]), or max_seq_length too long for the kernel's LDS staging.
+ * ------------------------------------------------------------------------------------------- */
+int lddl_collate_seqpack(lddl_ctx* ctx, void* stream, const uint8_t* d_bytes,
+                         const int64_t* d_a_off, const int64_t* d_b_off, const int32_t* d_na,
+                         const int32_t* d_nb, int32_t batch, const int64_t* d_dst,
+                         const int32_t* d_fill, const int32_t* d_seq_in_row,
+                         int32_t max_seq_length, int64_t* d_input_ids, int64_t* d_token_type_ids,
+                         int64_t* d_attention_mask, int64_t* d_special_tokens_mask,
+                         const uint8_t* d_lab_bytes, const int64_t* d_lab_off,
+                         const uint16_t* d_pos, const int64_t* d_pos_off, int64_t* d_labels,
+                         int64_t ignore_index, int64_t* d_position_ids, int64_t* d_sequence_ids);
+
+int lddl_collate_seqpack_masked(lddl_ctx* ctx, void* stream, const uint8_t* d_bytes,
+                                const int64_t* d_a_off, const int64_t* d_b_off,
+                                const int32_t* d_na, const int32_t* d_nb, int32_t batch,
+                                const int64_t* d_dst, const int32_t* d_fill,
+                                const int32_t* d_seq_in_row, int32_t max_seq_length,
+                                int32_t draw_stride, int64_t* d_input_ids,
+                                int64_t* d_token_type_ids, int64_t* d_attention_mask,
+                                int64_t* d_labels, int64_t* d_position_ids,
+                                int64_t* d_sequence_ids, float mlm_probability,
+                                int64_t ignore_index, int64_t vocab_len, uint64_t seed,
+                                uint64_t counter, int32_t whole_word);
+
 #ifdef __cplusplus
 }
 #endif

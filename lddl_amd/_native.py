@@ -96,6 +96,13 @@ SIGNATURES = {
     'lddl_collate_encode_masked_ww': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                      c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                                      ctypes.c_float, c_i64, c_i64, c_u64, c_u64]),
+    'lddl_collate_seqpack': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp,
+                                            c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    'lddl_collate_seqpack_masked': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                                   c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                                   c_vp, c_vp, c_vp, ctypes.c_float, c_i64, c_i64,
+                                                   c_u64, c_u64, c_i32]),
 }
 
 

@@ -1,12 +1,13 @@
 """Drop-in counterparts of lddl.torch (the reference's PyTorch loader package).
 
-`get_bert_pretrain_data_loader` is resolved lazily, so that DataLoader workers started with
-`spawn` / `forkserver` import only the worker-side modules (`packing`, `datasets`), never the
+`get_bert_pretrain_data_loader` and `get_bert_pretrain_packed_data_loader` (sequence packing,
+past the reference) are resolved lazily, so that DataLoader workers started with `spawn` /
+`forkserver` import only the worker-side modules (`packing`, `seqpack`, `datasets`), never the
 native library."""
 
 
 def __getattr__(name):
-    if name == 'get_bert_pretrain_data_loader':
-        from .bert import get_bert_pretrain_data_loader
-        return get_bert_pretrain_data_loader
+    if name in ('get_bert_pretrain_data_loader', 'get_bert_pretrain_packed_data_loader'):
+        from . import bert
+        return getattr(bert, name)
     raise AttributeError(name)

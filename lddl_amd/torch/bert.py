@@ -28,6 +28,7 @@ from .datasets import ParquetDataset  # noqa: F401
 from .log import DatasetLogger
 from .packing import (BertPretrainDataset, PackedBatch, _canon, _decode_record_batch,  # noqa: F401
                       _npy_u16, _ntok, _pack, _pack_batch)
+from .seqpack import SeqPackedBatch, plan_rows, seqpack_collate  # noqa: F401
 from .utils import get_node_rank, get_nproc_per_node, get_rank
 
 
@@ -225,6 +226,85 @@ def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=No
     return out
 
 
+def encode_seqpacked(spk, ctx, max_seq_length, sequence_length_alignment=8, ignore_index=-1,
+                     mask=None, events=None, stager=None, whole_word=False):
+    """`encode_packed` with several samples per row (past the reference): the
+    SeqPackedBatch `spk` carries the row plan made in the worker (`seqpack.plan_rows`).
+
+    Returns the [R, max_seq_length] tensors input_ids, token_type_ids, attention_mask, labels
+    (dynamic batches without `mask`: special_tokens_mask instead), position_ids (restart at every
+    sample) and sequence_ids (1-based index of the slot's sample in its row, 0 on padding: two
+    slots attend to each other iff they are in the same row and their ids are equal and not 0),
+    and per sample, in packed order (by row, then start): next_sentence_labels [B],
+    cls_positions [B] (flat slot of the sample's [CLS]: the NSP head gathers there) and
+    seq_lens [B] (int32).
+
+    mask, events, stager and whole_word are encode_packed's. The Philox stream is keyed per
+    sample and slot as in the unpacked batch of the same samples (whose row length is the longest
+    sample rounded up to sequence_length_alignment), so with equal (seed, counter) sample i's
+    segment holds bit for bit what encode_packed puts into row i. Static masking: a
+    masked_lm_positions value >= its own sample's length raises IndexError (in a packed row it
+    would land in the next sample)."""
+    dev = ctx.device
+    B = len(spk)
+    L = int(max_seq_length)
+    plan = spk.plan
+    if plan.capacity != L:
+        raise ValueError('the batch was planned for rows of {} slots, not {}'.format(
+            plan.capacity, L))
+    lens = (spk.na + spk.nb + 3).astype(np.int32)
+    stride = ((int(lens.max()) - 1) // sequence_length_alignment + 1) * sequence_length_alignment
+    order, R = plan.order, plan.R
+    dst = plan.row.astype(np.int64) * L + plan.start
+    host = [spk.blob,
+            np.concatenate([spk.a_off, spk.b_off, dst, spk.nsl[order], dst[order]]),
+            np.concatenate([spk.na, spk.nb, plan.fill, plan.seq_in_row, lens[order]])]
+    if spk.static:
+        lab_off, pos, pos_off = spk.extra
+        bad = pos >= np.repeat(lens, np.diff(pos_off))
+        if bad.any():
+            k = int(np.flatnonzero(bad)[0])
+            i = int(np.searchsorted(pos_off, k, side='right')) - 1
+            raise IndexError('masked_lm_positions of sample {} holds {} >= its length {}'.format(
+                i, int(pos[k]), int(lens[i])))
+        host += [lab_off, pos_off, pos.view(np.int16)]
+    staged = (stager or _stager_for(dev)).stage(host, dev)  # one H2D copy: batch and plan
+    d_blob, d_i64, d_i32 = staged[:3]
+    d_a, d_b, d_dst = d_i64[:B + 1], d_i64[B + 1:2 * B + 2], d_i64[2 * B + 2:3 * B + 2]
+    d_na, d_nb, d_fill, d_seq = (d_i32[k * B:(k + 1) * B] for k in range(4))
+    names = ('input_ids', 'token_type_ids', 'attention_mask', 'position_ids', 'sequence_ids')
+    fused = mask is not None and not spk.static
+    names += ('labels',) if fused or spk.static else ('special_tokens_mask',)
+    out = {k: torch.empty(R, L, dtype=torch.long, device=dev) for k in names}
+    head = (ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b), _ptr(d_na), _ptr(d_nb), B,
+            _ptr(d_dst), _ptr(d_fill), _ptr(d_seq), L)
+    if events is not None:
+        events[0].record()
+    if fused:
+        p, seed, counter = mask
+        check(lib.lddl_collate_seqpack_masked(
+            *head, stride, _ptr(out['input_ids']), _ptr(out['token_type_ids']),
+            _ptr(out['attention_mask']), _ptr(out['labels']), _ptr(out['position_ids']),
+            _ptr(out['sequence_ids']), float(p), ignore_index, len(ctx), seed, counter,
+            1 if whole_word else 0))
+    else:
+        d_lab_off = d_pos_off = d_pos = None
+        if spk.static:
+            d_lab_off, d_pos_off, d_pos = staged[3:]
+        check(lib.lddl_collate_seqpack(
+            *head, _ptr(out['input_ids']), _ptr(out['token_type_ids']),
+            _ptr(out['attention_mask']), _ptr(out.get('special_tokens_mask')),
+            _ptr(d_blob) if spk.static else None, _ptr(d_lab_off), _ptr(d_pos), _ptr(d_pos_off),
+            _ptr(out.get('labels')), ignore_index, _ptr(out['position_ids']),
+            _ptr(out['sequence_ids'])))
+    if events is not None:
+        events[1].record()
+    out['next_sentence_labels'] = d_i64[3 * B + 2:4 * B + 2]
+    out['cls_positions'] = d_i64[4 * B + 2:]
+    out['seq_lens'] = d_i32[4 * B:]
+    return out
+
+
 class _LazyContext:
     """The loader's HIP Context, created on first use: after the DataLoader workers of every bin
     have been started, so no worker is ever forked from a process holding this library's HIP
@@ -301,15 +381,33 @@ class GPUCollateLoader:
             # the batch shape is known on the host (counted in the worker): nothing here waits
             # for the GPU, the collate kernel is queued behind the consumer's training step
             with torch.no_grad():  # dynamic masking: collate + _mask_tokens in one kernel
-                enc = encode_packed(pk, ctx, self._align, self._ignore,
-                                    mask=(self._mlm, self._seed, self._counter), events=ev,
-                                    stager=self._stager, **self._mp)
+                enc = self._encode(pk, ctx, ev)
             if not pk.static:
                 self._counter += 1
             if self.stats is not None:
                 self.stats['events'].append(ev)
                 self.stats['slots'].append(enc['input_ids'].numel())
             yield self._extra(enc)
+
+    def _encode(self, pk, ctx, ev):
+        return encode_packed(pk, ctx, self._align, self._ignore,
+                             mask=(self._mlm, self._seed, self._counter), events=ev,
+                             stager=self._stager, **self._mp)
+
+
+class SeqPackCollateLoader(GPUCollateLoader):
+    """GPUCollateLoader over a DataLoader of SeqPackedBatch: the same batches, seeds and
+    counters, collated into rows of max_seq_length slots (R and every shape come with the plan
+    from the worker, so here too nothing waits for the GPU)."""
+
+    def __init__(self, loader, ctx, max_seq_length, *args, **kwargs):
+        super().__init__(loader, ctx, *args, **kwargs)
+        self._max_seq_length = max_seq_length
+
+    def _encode(self, spk, ctx, ev):
+        return encode_seqpacked(spk, ctx, self._max_seq_length, self._align, self._ignore,
+                                mask=(self._mlm, self._seed, self._counter), events=ev,
+                                stager=self._stager, whole_word=self._whole_word)
 
 
 def mask_seed(base_seed, rank, bin_id=-1):
@@ -324,6 +422,50 @@ class BertPretrainBinned(Binned):
         if isinstance(batch, dict):
             return batch['input_ids'].size(0)
         return len(batch[0]) if isinstance(batch, (list, tuple)) else len(batch)
+
+
+class BertPretrainPackedBinned(Binned):
+    """Binned over packing loaders: a batch's samples are its next_sentence_labels, not its
+    rows."""
+
+    def _get_batch_size(self, batch):
+        return batch['next_sentence_labels'].size(0)
+
+
+def get_bert_pretrain_packed_data_loader(path, max_seq_length, local_rank=0,
+                                         shuffle_buffer_size=16384,
+                                         shuffle_buffer_warmup_factor=16, tokenizer_class=None,
+                                         vocab_file=None, tokenizer_kwargs={},
+                                         data_loader_class=DataLoader, data_loader_kwargs={},
+                                         mlm_probability=0.15, base_seed=12345, log_dir=None,
+                                         log_level=logging.INFO, return_raw_samples=False,
+                                         start_epoch=0, sequence_length_alignment=8,
+                                         ignore_index=-1, whole_word_masking=False):
+    """`get_bert_pretrain_data_loader` with sequence packing (past the reference):
+    the samples of a batch share rows of `max_seq_length` slots instead of each being padded to
+    the batch's longest.
+
+    Same datasets, shuffle buffers, seeds and epoch / batch counters: with equal arguments batch
+    k holds the samples of batch k of `get_bert_pretrain_data_loader`, with the same masking,
+    rearranged. `batch_size` counts samples; the number of rows R varies per batch. The yielded
+    dict is `encode_seqpacked`'s: [R, max_seq_length] input_ids, token_type_ids, attention_mask,
+    labels, position_ids, sequence_ids and, per sample in packed order, next_sentence_labels,
+    cls_positions and seq_lens. sequence_length_alignment only keys the masking stream (the
+    unpacked batch's row length). A sample longer than max_seq_length raises ValueError; so does
+    return_raw_samples=True (nothing to pack), and whole_word_masking=True on a static-masking
+    dataset at its first batch. A `Binned` subclass over these loaders counts a batch's samples
+    as next_sentence_labels.size(0)."""
+    assert isinstance(max_seq_length, int) and not isinstance(max_seq_length, bool)
+    assert max_seq_length >= 3
+    assert isinstance(return_raw_samples, bool)
+    if return_raw_samples:
+        raise ValueError('return_raw_samples=True: raw samples are not packed; use '
+                         'get_bert_pretrain_data_loader')
+    return _bert_pretrain_data_loader(
+        path, local_rank, None, shuffle_buffer_size, shuffle_buffer_warmup_factor,
+        tokenizer_class, vocab_file, tokenizer_kwargs, data_loader_class, data_loader_kwargs,
+        mlm_probability, base_seed, log_dir, log_level, return_raw_samples, start_epoch,
+        sequence_length_alignment, ignore_index, whole_word_masking, seqpack_len=max_seq_length)
 
 
 def get_bert_pretrain_data_loader(path, local_rank=0, shuffle_buffer_size=16384,
@@ -355,10 +497,11 @@ def _bert_pretrain_data_loader(path, local_rank, dp_rank, shuffle_buffer_size,
                                tokenizer_kwargs, data_loader_class, data_loader_kwargs,
                                mlm_probability, base_seed, log_dir, log_level, return_raw_samples,
                                start_epoch, sequence_length_alignment, ignore_index,
-                               whole_word_masking=False):
+                               whole_word_masking=False, seqpack_len=None):
     """The loader of lddl.torch (dp_rank None) and of lddl.torch_mp (dp_rank given: files are
     strided and workers seeded by data-parallel rank, static batches carry the loss mask, and the
-    dynamic-masking key is the group's, so all ranks of a group yield the same batches)."""
+    dynamic-masking key is the group's, so all ranks of a group yield the same batches).
+    seqpack_len (lddl.torch only): the packing loader with rows of that many slots."""
     assert isinstance(path, str)
     assert isinstance(local_rank, int) and local_rank >= 0
     assert dp_rank is None or (isinstance(dp_rank, int) and dp_rank >= 0)
@@ -394,14 +537,21 @@ def _bert_pretrain_data_loader(path, local_rank, dp_rank, shuffle_buffer_size,
     if not return_raw_samples:  # the Context is created after the workers start (_LazyContext)
         ctx = _LazyContext(vocab_file, tokenizer_kwargs.get('do_lower_case', True))
         stager = HostStager()
-        data_loader_kwargs['collate_fn'] = _pack_batch
+        data_loader_kwargs['collate_fn'] = (_pack_batch if seqpack_len is None else
+                                            seqpack_collate(seqpack_len))
     data_loader_kwargs['persistent_workers'] = True
     mask_rank = get_rank() if dp_rank is None else dp_rank
+    binned_class = BertPretrainBinned if seqpack_len is None else BertPretrainPackedBinned
 
     def make(paths, bin_id=-1):
         dl = data_loader_class(BertPretrainDataset(paths, **dataset_kwargs), **data_loader_kwargs)
         if return_raw_samples:
             return dl
+        if seqpack_len is not None:
+            return SeqPackCollateLoader(dl, ctx, seqpack_len, mlm_probability, ignore_index,
+                                        sequence_length_alignment, extra_collate,
+                                        mask_seed(base_seed, mask_rank, bin_id), start_epoch,
+                                        stager, whole_word=whole_word_masking)
         return GPUCollateLoader(dl, ctx, mlm_probability, ignore_index,
                                 sequence_length_alignment, extra_collate,
                                 mask_seed(base_seed, mask_rank, bin_id), start_epoch, stager,
@@ -410,6 +560,6 @@ def _bert_pretrain_data_loader(path, local_rank, dp_rank, shuffle_buffer_size,
     paths = get_all_parquets_under(path)
     bin_ids = get_all_bin_ids(paths)
     if bin_ids:
-        return BertPretrainBinned([make(get_file_paths_for_bin_id(paths, b), b) for b in bin_ids],
-                                  base_seed=base_seed, start_epoch=start_epoch, logger=logger)
+        return binned_class([make(get_file_paths_for_bin_id(paths, b), b) for b in bin_ids],
+                            base_seed=base_seed, start_epoch=start_epoch, logger=logger)
     return make(paths)
