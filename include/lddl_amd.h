@@ -213,6 +213,13 @@ int lddl_bart_fill(lddl_ctx* ctx, void* stream, uint8_t* d_out, int64_t* d_chunk
  *   tokens[tok_off[q] : tok_off[q] + len_a[q]] = A (masked), then B up to tok_off[q+1];
  *   num_tokens = len(A)+len(B)+3; is_rn[q]; masked positions (sorted, in [CLS] A [SEP] B [SEP]
  *   coordinates) pos[pos_off[q]:pos_off[q+1]] with original-token labels lab[...].
+ * params->whole_word = 1 (with masking = 1 and rng = LDDL_RNG_NATIVE; any other combination fails
+ *   the call): whole-word masking as Google BERT's do_whole_word_mask. A word is a token that is
+ *   no continuation plus the continuations after it; a continuation is a "##x" vocab id that is
+ *   not first in A or B and does not follow a literal [CLS]/[SEP]. The pair's words are walked
+ *   in a random order and a word is masked iff it still fits the budget (the num_to_predict of
+ *   the per-token mode), so a pair has at most that many masked positions, possibly none;
+ *   counts[2] and pos_off are exact. The pairs themselves are those of whole_word = 0.
  * ------------------------------------------------------------------------------------------- */
 typedef struct lddl_pairs lddl_pairs;
 enum { LDDL_RNG_REPLAY = 0, LDDL_RNG_NATIVE = 1 };
@@ -224,6 +231,7 @@ typedef struct {
   double short_seq_prob;  /* --short-seq-prob */
   double masked_lm_ratio; /* --masked-lm-ratio */
   uint64_t native_seed;   /* counter-RNG key for LDDL_RNG_NATIVE */
+  int32_t whole_word;     /* --whole-word-masking (needs masking and LDDL_RNG_NATIVE) */
 } lddl_pair_params;
 int lddl_pairs_plan(lddl_ctx* ctx, void* stream, const lddl_pair_params* params,
                     const int64_t* d_sent_off, const int32_t* d_ids, const int32_t* d_sent_len,

@@ -110,7 +110,8 @@ class PairParams(ctypes.Structure):
     """lddl_pair_params (include/lddl_amd.h)."""
     _fields_ = [('seq', ctypes.c_int32), ('dup', ctypes.c_int32), ('masking', ctypes.c_int32),
                 ('rng', ctypes.c_int32), ('short_seq_prob', ctypes.c_double),
-                ('masked_lm_ratio', ctypes.c_double), ('native_seed', ctypes.c_uint64)]
+                ('masked_lm_ratio', ctypes.c_double), ('native_seed', ctypes.c_uint64),
+                ('whole_word', ctypes.c_int32)]
 
 
 RNG_REPLAY, RNG_NATIVE = 0, 1

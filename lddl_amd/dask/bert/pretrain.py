@@ -268,7 +268,8 @@ def make_batch_pairs(ctx, args, partitions, corpus, timer=None):
                     torch.from_numpy(part_doc_off).to(dev), torch.from_numpy(seeds).to(dev),
                     seq=args.target_seq_length, dup=args.duplicate_factor, masking=args.masking,
                     short_seq_prob=args.short_seq_prob, masked_lm_ratio=args.masked_lm_ratio,
-                    rng=getattr(args, 'rng', 'replay'), native_seed=args.seed)
+                    rng=getattr(args, 'rng', 'replay'), native_seed=args.seed,
+                    whole_word=getattr(args, 'whole_word_masking', False))
     tm('pairs')
     return pb
 
@@ -797,7 +798,12 @@ def main(args):
         raise ValueError('--num-shards writes balanced parquet shards only')
     if args.num_shards is not None and args.num_shards < 1:
         raise ValueError('--num-shards must be >= 1')
-    world = int(os.environ.get('WORLD_SIZE', '1'))
+    if getattr(args, 'whole_word_masking', False) and not (
+            args.masking and getattr(args, 'rng', 'replay') == 'native'):
+        raise ValueError('--whole-word-masking needs --masking and --rng native (replay '
+                         'reproduces the reference, which has no whole-word masking; without '
+                         '--masking the loaders mask: whole_word_masking=True there)')
+    world =int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     vocab = _resolve_vocab(args.vocab_file)
@@ -1006,6 +1012,10 @@ def attach_args(parser=None):
                     help_str='static masking in the preprocessor (default: off = dynamic '
                     'masking in the data loader)')
     parser.add_argument('--masked-lm-ratio', type=float, default=0.15, help='Default: 0.15')
+    attach_bool_arg(parser, 'whole-word-masking', default=False,
+                    help_str='lddl_amd, with --masking and --rng native: mask whole words '
+                    "(Google BERT's do_whole_word_mask); a pair gets at most the per-token "
+                    "mode's number of masked positions")
     parser.add_argument('--gpu-batch-bytes', type=int, default=512 << 20,
                         help='lddl_amd: input text bytes per GPU batch of partitions (bounds HBM '
                              'use; consecutive batches overlap their GPU work, rendering and file '

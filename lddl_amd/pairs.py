@@ -94,12 +94,25 @@ def _head_gather():
     return v == '1'
 
 
+def _check_whole_word(whole_word, masking, rng):
+    if whole_word and not masking:
+        raise ValueError('whole_word=True needs masking=True (without static masking the loaders '
+                         'mask: whole_word_masking=True there)')
+    if whole_word and rng != 'native':
+        raise ValueError("whole_word=True needs rng='native' (the replay mode reproduces the "
+                         'reference, which has no whole-word masking)')
+
+
 def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_seed, seq=128,
                dup=5, masking=False, short_seq_prob=0.1, masked_lm_ratio=0.15, rng='replay',
-               native_seed=12345, _capacity_scale=1.0, _trace=None):
+               native_seed=12345, _capacity_scale=1.0, _trace=None, *, whole_word=False):
     """All inputs are cuda tensors (int64 offsets / seeds; tokenizer output from Context.tokenize).
 
     rng='replay' reproduces CPython `random` after random.seed(part_seed[p]) per partition.
+
+    whole_word=True (with masking=True and rng='native' only) masks whole words, as Google BERT's
+    do_whole_word_mask: the same pairs as whole_word=False, each with at most the per-token
+    mode's number of masked positions, possibly none.
 
     A large replay batch with static masking is planned in two partition ranges
     (include/lddl_amd.h, lddl_pairs_plan_head): the first range's pairs are gathered, into
@@ -107,9 +120,10 @@ def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_se
     (_capacity_scale: tests only, scales those sizes to force the regrow path; _trace: a dict
     that receives which path ran.)
     """
+    _check_whole_word(whole_word, masking, rng)
     dev = ctx.device
     prm = PairParams(seq, dup, int(bool(masking)), RNG_REPLAY if rng == 'replay' else RNG_NATIVE,
-                     short_seq_prob, masked_lm_ratio, native_seed)
+                     short_seq_prob, masked_lm_ratio, native_seed, int(bool(whole_word)))
     n_sent = sent_off.numel() - 1
     n_doc = doc_sent_off.numel() - 1
     n_part = part_doc_off.numel() - 1
@@ -181,13 +195,15 @@ def _side_stream(dev):
 
 
 def tokenize_and_pair_chunked(ctx, text, sent_off, doc_sent_off, part_doc_off, part_seed,
-                              n_chunks=2, max_pieces=512, tok_stream=None, **pair_kw):
+                              n_chunks=2, max_pieces=512, tok_stream=None, whole_word=False,
+                              **pair_kw):
     """tokenize + make_pairs over `n_chunks` partition-aligned chunks, pipelined on two streams:
     every chunk's tokenizer is queued on a side stream, each chunk's pair planner on the current
     stream waits only for its own chunk's tokens, so chunk k+1 is tokenized while chunk k is
     planned and gathered. Partitions are independent (per-partition seeds), so the result is
     bit-identical to one call over all partitions. Returns the chunks' PairBatch list in
     partition order."""
+    _check_whole_word(whole_word, pair_kw.get('masking', False), pair_kw.get('rng', 'replay'))
     n_part = part_doc_off.numel() - 1
     cuts = [round(k * n_part / n_chunks) for k in range(n_chunks + 1)]
     pc = torch.tensor(cuts, dtype=torch.int64, device=part_doc_off.device)
@@ -214,7 +230,7 @@ def tokenize_and_pair_chunked(ctx, text, sent_off, doc_sent_off, part_doc_off, p
             x.record_stream(main)
         pb = make_pairs(ctx, so, ids, sl, doc_sent_off[d_cut[k]:d_cut[k + 1] + 1] - s_cut[k],
                         part_doc_off[cuts[k]:cuts[k + 1] + 1] - d_cut[k],
-                        part_seed[cuts[k]:cuts[k + 1]], **pair_kw)
+                        part_seed[cuts[k]:cuts[k + 1]], whole_word=whole_word, **pair_kw)
         del ids
         out.append(pb)
     return out
