@@ -247,7 +247,8 @@ int lddl_pairs_emit(lddl_pairs* plan, void* stream, void* d_tokens, int64_t* d_t
  * head on `stream`, the tail on a side stream of the context (ordered by events only). The pairs
  * of the head are a prefix of the output and final once the head is planned.
  *   lddl_pairs_plan_head: inputs as lddl_pairs_plan. head[8] = {split, head pairs, head tokens,
- *     head masked positions, suggested capacity for pairs, for tokens, for masked positions, 0}.
+ *     head masked positions, suggested capacity for pairs, for tokens, for masked positions,
+ *     hand-offs of a time-sliced plan (below; 0 when the plan was not sliced)}.
  *     split = 0: the plan is complete and one range; call lddl_pairs_plan_tail for the counts and
  *     lddl_pairs_emit. split = 1: the tail's planner is still running. The capacities are the
  *     head's counts scaled by kept tokens (all) / kept tokens (head) plus a margin: outputs
@@ -264,7 +265,16 @@ int lddl_pairs_emit(lddl_pairs* plan, void* stream, void* d_tokens, int64_t* d_t
  *     exactly what lddl_pairs_emit writes.
  * lddl_pairs_plan = lddl_pairs_plan_head + lddl_pairs_plan_tail. LDDL_PLAN_SPLIT (environment,
  * A/B): unset or -1 = automatic, 0 = never split, k > 0 = a head of exactly min(k, n_part)
- * partitions; any other value fails the call. */
+ * partitions; any other value fails the call.
+ * (Automatic: never, since a batch of more partitions than the device holds planner workgroups
+ * is time-sliced instead, below; the split plan runs when LDDL_PLAN_SPLIT forces it, or with
+ * LDDL_PLAN_SLICE=0.)
+ * LDDL_PLAN_SLICE (environment, A/B): the time-sliced replay plan, one range planned by as many
+ * persistent planner waves as the device holds, each working on a partition for a quantum of
+ * documents before it parks it and takes the next from a queue. Unset or -1 = automatic, 0 =
+ * never, k > 0 = always, with a quantum of k documents; any other value fails the call, and so
+ * does a positive value together with a positive LDDL_PLAN_SPLIT (a split plan is not sliced).
+ * LDDL_PLAN_WAVES = g >= 1 overrides the number of persistent waves. */
 int lddl_pairs_plan_head(lddl_ctx* ctx, void* stream, const lddl_pair_params* params,
                          const int64_t* d_sent_off, const int32_t* d_ids, const int32_t* d_sent_len,
                          int64_t n_sent, const int64_t* d_doc_sent_off, int64_t n_doc,

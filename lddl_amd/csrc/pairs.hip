@@ -536,6 +536,15 @@ struct PlanArgs {
   int64_t* part_npairs;
   uint64_t* stamps;  // diagnostic build: [n_part][8]
   uint64_t* tl;      // diagnostic build: [n_part][2] s_memrealtime at start / end (100 MHz)
+  // time-sliced mode (plan_replay_kernel<.., true>; see "The time-sliced mode" below)
+  unsigned* sl_ctl;   // [0] tickets claimed, [1] ring entries reserved (= hand-offs),
+                      // [2] dense groups claimed, [3] unused; zeroed with the ring on every launch
+  unsigned* sl_ring;  // [sl_ring_cap] 0 = not published, partition + 1, or kRingAbandoned
+  uint64_t* sl_save;  // [n_part][kSaveU64] a parked partition's state
+  int32_t sl_ring_cap;
+  int32_t sl_dense;    // 1: the waves that leave the queue pack `dense`
+  int32_t sl_quantum;  // documents per slice; 0: 1/kPlanSliceK of the partition's dup * documents
+  uint64_t* tls;       // diagnostic build: [n_part + sl_ring_cap][2] slice start / end by ticket
 };
 
 constexpr int kDocLds = 512;  // partitions with <= this many documents cache offsets in LDS
@@ -681,14 +690,98 @@ __device__ inline void densify_group(int64_t k0, const int64_t* __restrict__ ks_
 // (profiles/r02_plan_minw_ab.txt)
 // kDocsLds: every partition's document offsets fit the LDS table (host-checked: <= kDocLds
 // documents), so the document lookups carry no global-memory branch; kJB: bytes per shuffle draw
-template <bool kDocsLds, int kJB>
+//
+// The time-sliced mode (kSliced; a one-range plan of more partitions than the device holds
+// waves). The grid is persistent one-wave workgroups, as many as the device holds. A wave plans
+// a partition for a quantum of documents, parks it at the document boundary and takes the next
+// item of a global FIFO, so every partition gets slice k before any gets slice k + 1 and all
+// the chains end together, with every wave slot busy until then.
+//   Tickets, all claimed by a returning add on sl_ctl[0], the first one when the wave starts: a
+//   workgroup owns no work by its index, so one that becomes resident late (measured with the
+//   first tickets bound to the workgroup index: 1,024 of 7,168 started when the others left and
+//   planned their partitions alone, 152 ms) finds the queue as it then is. Ticket t < n_part is
+//   the fresh partition t (seeded as in the one-shot mode), ticket n_part + r is entry r of a
+//   ring that never wraps (the host sizes it from the quantum: plan_slice_ring_entries).
+//   Parking. The wave writes the partition's state (the MT block with its look-ahead, mti, the
+//   loop position, np and the partition's pool chunks: kSaveU64 granules) to the partition's save
+//   area with write-through agent-scope stores, drains them (s_waitcnt vmcnt(0)), reserves a ring
+//   index with one returning add on sl_ctl[1] and publishes partition + 1 there by an atomic
+//   exchange. Then it claims its next ticket.
+//   Claiming. The claimant of ring entry r exchanges kRingAbandoned into it. A partition id
+//   coming back is its work item: one agent-scope acquire, then the state is read by vector loads
+//   (lane-indexed addresses, through LDS; the uniform words become scalars by readfirstlane). Zero
+//   coming back (after kPopTries looks: the entry is reserved but not yet written, or the ring is
+//   empty) means the wave leaves the queue for good.
+//   No wave waits for another, and nothing is lost: the exchanges on one ring word are totally
+//   ordered, so either the claimant sees the partition id and owns the partition, or the
+//   publisher sees kRingAbandoned and keeps its partition for another slice (it alone ever held
+//   it). Every ticket below the final sl_ctl[0] has exactly one claimant, and the final count
+//   covers every published entry: each slice end (a parking that was not handed back, or a
+//   finished partition) is followed by one claim, which makes n_part + published - abandoned
+//   claims on top of the waves' first ones, and no more entries are ever abandoned than there are
+//   waves (a wave abandons one entry, then leaves). So no workgroup's progress depends on another
+//   being resident, and the launch ends whatever the dispatch order.
+//   The pool chunks belong to the partition here (parked with it), not to the wave: the pools'
+//   total use is then the same whichever wave plans which slice, which the exact-size re-plan
+//   after a pool overflow relies on.
+//   A wave that leaves the queue packs `dense`: groups of kept sentences claimed from sl_ctl[2].
+constexpr int kSaveHdr = 16;                            // header words behind the MT block
+constexpr int kSaveU64 = (kN + kLook + kSaveHdr) / 2;   // 8-byte granules per parked partition
+constexpr int kPopTries = 4;                            // looks at a ring entry that reads zero
+constexpr unsigned kRingAbandoned = 0xFFFFFFFFu;
+constexpr int kDenseClaim = 4;                          // 64-sentence groups per claim
+static_assert((kN + kLook + kSaveHdr) % 2 == 0 && kSaveHdr <= kDocLds, "save area layout");
+
+#define LDDL_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+// Claims the wave's next ticket (uniform): -1 = leave the queue, else the ticket, with *part the
+// partition to plan (fresh when ticket < n_part, else parked).
+__device__ inline int32_t slice_claim(const PlanArgs& A, int32_t* part) {
+  int32_t t_out = -1, p_out = 0;
+  if (threadIdx.x == 0) {
+    const unsigned t = __hip_atomic_fetch_add(&A.sl_ctl[0], 1u, LDDL_RLX_AGENT);
+    if (t < (unsigned)A.n_part) {
+      t_out = (int32_t)t;
+      p_out = (int32_t)t;
+    } else if (t - (unsigned)A.n_part < (unsigned)A.sl_ring_cap) {
+      unsigned* e = A.sl_ring + (t - (unsigned)A.n_part);
+      for (int tries = 1; tries < kPopTries; ++tries) {  // (bounded: then the exchange decides)
+        if (__hip_atomic_load(e, LDDL_RLX_AGENT) != 0) break;
+        __builtin_amdgcn_s_sleep(4);
+      }
+      const unsigned v = __hip_atomic_exchange(e, kRingAbandoned, LDDL_RLX_AGENT);
+      if (v != 0 && v != kRingAbandoned) {
+        t_out = (int32_t)t;
+        p_out = (int32_t)(v - 1);
+      }
+    }
+  }
+  *part = uni(p_out);
+  return uni(t_out);
+}
+
+// Publishes the parked partition p (its state is stored and drained). true: handed on; false: the
+// entry had been abandoned (or the ring is full), the wave keeps the partition.
+__device__ inline bool slice_publish(const PlanArgs& A, int32_t p) {
+  int32_t on = 0;
+  if (threadIdx.x == 0) {
+    const unsigned r = __hip_atomic_fetch_add(&A.sl_ctl[1], 1u, LDDL_RLX_AGENT);
+    if (r < (unsigned)A.sl_ring_cap)
+      on = __hip_atomic_exchange(A.sl_ring + r, (unsigned)p + 1u, LDDL_RLX_AGENT) == 0;
+  }
+  // the publish is complete before the wave's own claim reads the queue
+  __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  return uni(on) != 0;
+}
+
+template <bool kDocsLds, int kJB, bool kSliced = false>
 __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   uint32_t* s_mt = reinterpret_cast<uint32_t*>(smem);
   int32_t* s_doc = reinterpret_cast<int32_t*>(s_mt + kN + kLook);  // [kDocLds + 1]
   const int lane = threadIdx.x;
   const bool leader = lane == 0;
-  if ((int)blockIdx.x >= A.n_part) {
+  if (!kSliced && (int)blockIdx.x >= A.n_part) {
     // Workgroups past the partitions pack `dense` (what densify_kernel would do after this
     // launch). Dispatched in order, they start as the last partitions' waves are placed and
     // run in the slots the planner's tail leaves idle (a separate launch before or beside the
@@ -698,7 +791,15 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
       densify_group(k_lo + g * 64, A.ks_start, A.ks_len, A.kscan, A.n_kept_sent, A.ids, A.dense);
     return;
   }
-  const int p = A.p0 + (int)blockIdx.x;
+  // sliced: the wave's current ticket and whether the partition is taken up from its save area
+  [[maybe_unused]] int32_t ticket = 0;
+  [[maybe_unused]] bool parked = false;
+  int p = A.p0 + (int)blockIdx.x;
+  if constexpr (kSliced) {
+    ticket = slice_claim(A, &p);
+    parked = ticket >= A.n_part;
+  }
+  if (!kSliced || ticket >= 0) do {  // (sliced: one slice per turn; else the body runs once)
 #ifdef LDDL_STAMPS
   uint64_t st_acc[kStampRegions] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -711,7 +812,39 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
               , 0, 0
 #endif
   };
-  rng.seed_i64(A.part_seed[p]);
+  // this wave's current chunks of the mask pool and of the shuffle-draw pool: next entry, entries
+  // left (32-bit compares), and whether the chunk lies inside the pool
+  int64_t pool_cur = 0, jpool_cur = 0;
+  int32_t pool_left = 0, jpool_left = 0;
+  bool pool_fits = true, jpool_fits = true;
+  int64_t np = 0;
+  // sliced: where the slice starts (dp0, di0), and the documents left in it
+  [[maybe_unused]] int dp0 = 0;
+  [[maybe_unused]] int32_t di0 = 0, slice_left = 0;
+  [[maybe_unused]] bool yielded = false;
+  if (kSliced && parked) {
+    // the one acquire of the hand-off, then the state by vector loads (lane-indexed addresses)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    uint64_t* sv = A.sl_save + (int64_t)p * kSaveU64;
+    uint64_t* s64 = reinterpret_cast<uint64_t*>(s_mt);
+    for (int i = lane; i < kSaveU64; i += 64) s64[i] = sv[i];
+    __syncthreads();
+    const int32_t* h = s_doc;  // the header words follow the MT block
+    rng.mti = uni(h[0]);
+    dp0 = uni(h[1]);
+    di0 = uni(h[2]);
+    np = ((int64_t)uni(h[11]) << 32) | (uint32_t)uni(h[3]);
+    pool_cur = ((int64_t)uni(h[5]) << 32) | (uint32_t)uni(h[4]);
+    pool_left = uni(h[6]);
+    jpool_cur = ((int64_t)uni(h[8]) << 32) | (uint32_t)uni(h[7]);
+    jpool_left = uni(h[9]);
+    const int32_t fb = uni(h[10]);
+    pool_fits = (fb & 1) != 0;
+    jpool_fits = (fb & 2) != 0;
+    __syncthreads();  // (before the document table overwrites the header)
+  } else {
+    rng.seed_i64(A.part_seed[p]);
+  }
   const int64_t d0 = A.kp_off[p];
   const int32_t nd = (int32_t)(A.kp_off[p + 1] - d0);  // (partition-local indices are 32-bit)
   const int64_t kbase = A.kd_off[d0];
@@ -725,13 +858,7 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
   const int32_t* ks_len_p = A.ks_len + kbase;
   const int64_t base = (int64_t)A.dup * kbase;
   const int32_t max_num = A.seq - 3;
-  // this wave's current chunks of the mask pool and of the shuffle-draw pool: next entry, entries
-  // left (32-bit compares), and whether the chunk lies inside the pool
-  int64_t pool_cur = 0, jpool_cur = 0;
-  int32_t pool_left = 0, jpool_left = 0;
-  bool pool_fits = true, jpool_fits = true;
   LenWin La, Lb;
-  int64_t np = 0;
   constexpr int kPrioLevels = 4;  // priority levels used (s_setprio has 4)
   // issue priority by progress: a SIMD issues its highest-priority (then oldest) wave first, so
   // waves that are behind (e.g. a partition dispatched into a freed slot) catch up and the waves
@@ -741,10 +868,40 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
   // the priority steps at the document counts where progress crosses a quarter (no 64-bit
   // division per document)
   int32_t prio_next = 0, prio_done = 0;
-  if (nd > 0) La.prefetch(ks_len_p + doc_loc(0), doc_loc(1) - doc_loc(0));
-  for (int dp = 0; dp < A.dup; ++dp) {
-    for (int32_t di = 0; di < nd; ++di) {
-      if (prio_done >= prio_next) {
+  if constexpr (kSliced) {  // the slice's quantum (plan_slice_quantum, per partition)
+    const int64_t q = A.sl_quantum ? (int64_t)A.sl_quantum
+                                   : (prio_tot + kPlanSliceK - 1) / kPlanSliceK;
+    slice_left = (int32_t)std::min<int64_t>(std::max<int64_t>(q, 1), INT32_MAX);
+  }
+  if (nd > 0) La.prefetch(ks_len_p + doc_loc(di0), doc_loc(di0 + 1) - doc_loc(di0));
+  for (int dp = dp0; dp < A.dup; ++dp) {
+    for (int32_t di = di0; di < nd; ++di) {
+      if constexpr (kSliced) {
+        if (slice_left == 0) {
+          // The quantum is used up and document (dp, di) is still to plan: park the partition.
+          // The header words go behind the MT block in LDS (over the document table, which the
+          // next slice loads again), then the block leaves as 8-byte write-through stores.
+          int32_t hw = 0;
+          const int32_t hv[12] = {rng.mti, dp, di, (int32_t)np, (int32_t)pool_cur,
+                                  (int32_t)(pool_cur >> 32), pool_left, (int32_t)jpool_cur,
+                                  (int32_t)(jpool_cur >> 32), jpool_left,
+                                  (pool_fits ? 1 : 0) | (jpool_fits ? 2 : 0), (int32_t)(np >> 32)};
+#pragma unroll
+          for (int k = 0; k < 12; ++k)
+            if (lane == k) hw = hv[k];
+          __syncthreads();
+          if (lane < kSaveHdr) s_doc[lane] = hw;
+          __syncthreads();
+          uint64_t* sv = A.sl_save + (int64_t)p * kSaveU64;
+          const uint64_t* s64 = reinterpret_cast<const uint64_t*>(s_mt);
+          for (int i = lane; i < kSaveU64; i += 64) __hip_atomic_store(sv + i, s64[i], LDDL_RLX_AGENT);
+          __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drained before the publish
+          yielded = true;
+          break;
+        }
+        --slice_left;
+      }
+      if (!kSliced && prio_done >= prio_next) {
         ++prio_q;
         prio_next = (int32_t)(((int64_t)(prio_q + 1) * prio_tot + kPrioLevels - 1) / kPrioLevels);
         const int lvl = kPrioLevels - 1 - prio_q;
@@ -894,7 +1051,12 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
         chunk0 = next0;
       }
     }
+    if constexpr (kSliced) {
+      if (yielded) break;
+      di0 = 0;  // (the later passes start at the partition's first document)
+    }
   }
+  if (!kSliced || !yielded) {
   // random.shuffle(partition_pairs) (pretrain.py:401): record the draws j_i, i = np-1 .. 1
   // (64 at a time through writelane); shuffle_sort_kernel resolves the swaps.
   STAMP_ADD(0, st_t);
@@ -903,7 +1065,20 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
     rng.fy_draws(np, [&](int32_t i, uint32_t j) { js[i] = (int32_t)j; });  // (js[0] is never read)
   }
   STAMP_ADD(6, st_t);
+  }
 #ifdef LDDL_STAMPS
+  if constexpr (kSliced) {  // the slices' regions add up per partition; the timeline is per ticket
+    if (leader && A.stamps)
+      for (int r = 0; r < kStampRegions - 1; ++r)
+        atomicAdd(reinterpret_cast<unsigned long long*>(A.stamps) + (int64_t)p * kStampRegions + r,
+                  (unsigned long long)st_acc[r]);
+    if (leader && A.tl && !parked) A.tl[2 * (int64_t)p] = rt0;
+    if (leader && A.tl && !yielded) A.tl[2 * (int64_t)p + 1] = __builtin_amdgcn_s_memrealtime();
+    if (leader && A.tls && ticket >= 0) {
+      A.tls[2 * (int64_t)ticket] = rt0;
+      A.tls[2 * (int64_t)ticket + 1] = __builtin_amdgcn_s_memrealtime();
+    }
+  } else {
   st_acc[7] = rng.n_pass * 1000000 / (rng.n_win ? rng.n_win : 1);  // passes per window x 1e6
   if (leader && A.stamps)
     for (int r = 0; r < kStampRegions; ++r) A.stamps[(int64_t)p * kStampRegions + r] = st_acc[r];
@@ -911,8 +1086,37 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
     A.tl[2 * (int64_t)p] = rt0;
     A.tl[2 * (int64_t)p + 1] = __builtin_amdgcn_s_memrealtime();
   }
+  }
 #endif
-  if (leader) A.part_npairs[p] = np;
+  if (!kSliced || !yielded) {
+    if (leader) A.part_npairs[p] = np;
+  }
+  if constexpr (kSliced) {
+    // a parked partition goes to the ring's end, unless its entry comes back abandoned: then the
+    // wave keeps it (ticket -1: no claim) and takes it up from the save area like any other
+    parked = yielded && !slice_publish(A, p);
+    if (parked) {
+      ticket = -1;
+    } else {
+      ticket = slice_claim(A, &p);
+      parked = ticket >= A.n_part;
+    }
+    if (ticket < 0 && !parked) break;
+  }
+  } while (kSliced);
+  if constexpr (kSliced) {
+    // out of the queue: pack `dense` (what the one-shot launch's extra workgroups do)
+    const int64_t n_grp = A.sl_dense ? (A.n_kept_sent + 63) / 64 : 0;
+    while (n_grp) {
+      int32_t g0 = 0;
+      if (leader) g0 = (int32_t)__hip_atomic_fetch_add(&A.sl_ctl[2], (unsigned)kDenseClaim, LDDL_RLX_AGENT);
+      g0 = uni(g0);
+      if ((int64_t)(uint32_t)g0 >= n_grp) break;
+      for (int g = 0; g < kDenseClaim && (int64_t)(uint32_t)g0 + g < n_grp; ++g)
+        densify_group(((int64_t)(uint32_t)g0 + g) * 64, A.ks_start, A.ks_len, A.kscan, A.n_kept_sent,
+                      A.ids, A.dense);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2470,6 +2674,8 @@ struct PlanWork {
   ArenaScope& tmp;
   FyKnobs fy;
   int64_t split_knob = -1;  // LDDL_PLAN_SPLIT
+  int64_t slice_knob = -1;  // LDDL_PLAN_SLICE
+  int64_t waves_knob = -1;  // LDDL_PLAN_WAVES
   // compact_inputs
   int64_t* scratch = nullptr;  // scan scratch of the compaction and of the re-plan loop
   int64_t n_kept_tok = 0;
@@ -2490,13 +2696,19 @@ struct PlanWork {
   int64_t* split_info = nullptr;  // split_info_kernel's two values, and their host copies
   int64_t h_split_info[2] = {0, 0};
   int64_t* tail_rel = nullptr;  // the tail partitions' first pairs, relative to the range
+  // the time-sliced plan (one range): the queue block (4 control words + the ring, zeroed before
+  // every launch), the partitions' save areas and the persistent grid
+  bool sliced = false;
+  unsigned* sl_queue = nullptr;
+  int64_t sl_ring_cap = 0, sl_grid = 0;
+  int sl_dense = 1;  // LDDL_PLAN_SLICE_DENSE (A/B): who packs `dense`, see launch_planner
   // shuffle_partitions
   PairMaps M{nullptr, nullptr, nullptr, nullptr};
   // layout
   int2* pcnt = nullptr;
   int64_t* scr2 = nullptr;
 #ifdef LDDL_STAMPS
-  uint64_t *d_stamps = nullptr, *d_tl = nullptr;
+  uint64_t *d_stamps = nullptr, *d_tl = nullptr, *d_tls = nullptr;
 #endif
 };
 
@@ -2514,6 +2726,7 @@ struct PairRange {
 struct lddl_pairs {
   int32_t masking = 0, max_pred = 0, seq = 0, cls_id = -1, sep_id = -1;
   int64_t n_part = 0, n_pairs = 0, n_tokens = 0, n_masked = 0, n_kept_sent = 0, n_kept_doc = 0;
+  int64_t n_slices = 0;  // hand-offs of a time-sliced plan (0: not sliced, or no partition parked)
   // every device block of the plan, from the context's arena (the context outlives its plans);
   // lddl_pairs_destroy gives them back on its stream, a plan dropped while planning on the
   // planning stream
@@ -2591,7 +2804,33 @@ static int read_split_knob(int64_t* k) {
   return 0;
 }
 
-static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKnobs* fy, int64_t* split_knob) {
+// A/B knob of the time-sliced replay plan, LDDL_PLAN_SLICE: unset or -1 = automatic
+// (plan_slice_on), 0 = never, k > 0 = always, with a quantum of k documents. LDDL_PLAN_WAVES
+// (tests and A/B): the persistent grid of a sliced plan, g >= 1 workgroups (unset or -1: what the
+// device holds at once).
+static int read_slice_knobs(int64_t split_knob, int64_t* slice, int64_t* waves) {
+  *slice = *waves = -1;
+  if (const char* e = getenv("LDDL_PLAN_SLICE")) {
+    char* end = nullptr;
+    const long long v = strtoll(e, &end, 10);
+    if (end == e || *end || v < -1)
+      LDDL_FAIL(-1, "LDDL_PLAN_SLICE must be -1 (auto), 0 or a quantum of documents");
+    *slice = v;
+  }
+  if (const char* e = getenv("LDDL_PLAN_WAVES")) {
+    char* end = nullptr;
+    const long long v = strtoll(e, &end, 10);
+    if (end == e || *end || v < -1 || v == 0 || v > (1 << 20))
+      LDDL_FAIL(-1, "LDDL_PLAN_WAVES must be -1 (auto) or a workgroup count up to 2^20");
+    *waves = v;
+  }
+  if (split_knob > 0 && *slice > 0)
+    LDDL_FAIL(-1, "LDDL_PLAN_SPLIT and LDDL_PLAN_SLICE are both forced: a split plan is not sliced");
+  return 0;
+}
+
+static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKnobs* fy, int64_t* split_knob,
+                           int64_t* slice_knob, int64_t* waves_knob) {
   if (!c || !prm) LDDL_FAIL(-1, "null argument");
   if (prm->seq < 5 || prm->seq > 65535) LDDL_FAIL(-1, "target_seq_length %d out of range", prm->seq);
   if (prm->dup < 1) LDDL_FAIL(-1, "duplicate_factor must be >= 1");
@@ -2607,7 +2846,8 @@ static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKno
     LDDL_FAIL(-1, "whole_word needs rng = LDDL_RNG_NATIVE (the replay mode reproduces the "
                   "reference, which has no whole-word masking)");
   int rc;
-  if ((rc = read_split_knob(split_knob))) return rc;
+  if ((rc = read_split_knob(split_knob)) || (rc = read_slice_knobs(*split_knob, slice_knob, waves_knob)))
+    return rc;
   return read_fy_knobs(fy);
 }
 
@@ -2900,6 +3140,9 @@ static int plan_replay_setup(lddl_pairs* P, PlanWork& W) {
 typedef void (*PlanKernel)(PlanArgs);
 static PlanKernel planner_kernel(const PlanWork& W) {
   const bool docs_lds = W.max_docs + 1 <= (unsigned long long)kDocLds;  // document table in LDS
+  if (W.sliced)
+    return docs_lds ? (W.A.jbytes == 1 ? plan_replay_kernel<true, 1, true> : plan_replay_kernel<true, 2, true>)
+                    : (W.A.jbytes == 1 ? plan_replay_kernel<false, 1, true> : plan_replay_kernel<false, 2, true>);
   return docs_lds ? (W.A.jbytes == 1 ? plan_replay_kernel<true, 1> : plan_replay_kernel<true, 2>)
                   : (W.A.jbytes == 1 ? plan_replay_kernel<false, 1> : plan_replay_kernel<false, 2>);
 }
@@ -2907,17 +3150,62 @@ constexpr size_t kPlanLds = 4 * (kN + kLook) + 4 * (kDocLds + 4) + 16;  // ~4.8 
 
 // The head range of a split replay plan with static masking (0: one range): what the device
 // holds of the planner's one-wave workgroups at once, see plan_split_point.
+// planner workgroups (one wave each) the device holds at once, for the instantiation W selects
+static int planner_capacity(const PlanWork& W, int64_t* capacity) {
+  int per_cu = 0, n_cu = 0;
+  LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, planner_kernel(W), 64, kPlanLds));
+  LDDL_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, W.c->device));
+  *capacity = (int64_t)per_cu * n_cu;
+  return 0;
+}
+
 static int choose_split(const PlanWork& W, int64_t* s) {
   *s = 0;
-  if (!W.prm->masking || W.n_part <= 0 || W.split_knob == 0) return 0;
+  if (W.sliced || !W.prm->masking || W.n_part <= 0 || W.split_knob == 0) return 0;
   int64_t capacity = 0;
-  if (W.split_knob < 0) {
-    int per_cu = 0, n_cu = 0;
-    LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, planner_kernel(W), 64, kPlanLds));
-    LDDL_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, W.c->device));
-    capacity = (int64_t)per_cu * n_cu;
-  }
+  int rc;
+  if (W.split_knob < 0 && (rc = planner_capacity(W, &capacity))) return rc;
   *s = plan_split_point(W.n_part, capacity, W.split_knob);
+  return 0;
+}
+
+// Whether the plan runs time-sliced in one range (plan_slice_on; with or without masking; a
+// forced split keeps the split path), and then its grid, ring and save areas.
+static int choose_slice(const lddl_pairs* P, PlanWork& W) {
+  W.sliced = false;
+  if (W.n_part <= 0 || W.split_knob > 0 || W.slice_knob == 0) return 0;
+  if (W.slice_knob < 0 && !kPlanSliceAuto) return 0;
+  int64_t capacity = 0;
+  int rc;
+  W.sliced = true;  // (the capacity of the sliced instantiation)
+  rc = planner_capacity(W, &capacity);
+  W.sliced = !rc && plan_slice_on(W.n_part, capacity, W.slice_knob);
+  if (rc || !W.sliced) return rc;
+  W.sl_grid = std::min<int64_t>(W.n_part, W.waves_knob > 0 ? W.waves_knob : std::max<int64_t>(capacity, 1));
+  W.sl_dense = env_int("LDDL_PLAN_SLICE_DENSE", 1);
+  if (W.sl_dense < 0 || W.sl_dense > 2) LDDL_FAIL(-1, "LDDL_PLAN_SLICE_DENSE must be 0, 1 or 2");
+  const unsigned __int128 units = (unsigned __int128)(uint64_t)W.prm->dup * (uint64_t)P->n_kept_doc;
+  W.sl_ring_cap = plan_slice_ring_entries(
+      W.n_part, units > (unsigned __int128)INT64_MAX ? INT64_MAX : (int64_t)units, W.slice_knob);
+  // tickets and dense-group claims are 32-bit counters
+  if (W.sl_ring_cap >= INT32_MAX - W.n_part || P->n_kept_sent / 64 >= INT32_MAX - (int64_t)(1 << 24))
+    LDDL_FAIL(-1, "batch too large for the time-sliced plan (LDDL_PLAN_SLICE=0, or smaller GPU batches)");
+  uint64_t* save;
+  if ((rc = W.tmp.take(&W.sl_queue, 4 + ((W.sl_ring_cap + 3) & ~(int64_t)3))) ||
+      (rc = W.tmp.take(&save, W.n_part * kSaveU64)))
+    return rc;
+  PlanArgs& A = W.A;
+  A.sl_ctl = W.sl_queue;
+  A.sl_ring = W.sl_queue + 4;
+  A.sl_save = save;
+  A.sl_ring_cap = (int32_t)W.sl_ring_cap;
+  A.sl_dense = W.sl_dense == 1;
+  A.sl_quantum = (int32_t)std::min<int64_t>(std::max<int64_t>(W.slice_knob, 0), INT32_MAX);
+#ifdef LDDL_STAMPS
+  if ((rc = W.tmp.take(&W.d_tls, 2 * (W.n_part + W.sl_ring_cap)))) return rc;
+  LDDL_HIP(hipMemsetAsync(W.d_tls, 0, 16 * (W.n_part + W.sl_ring_cap), W.st));
+  A.tls = W.d_tls;
+#endif
   return 0;
 }
 
@@ -2951,6 +3239,22 @@ static int launch_planner(const PlanWork& W, int64_t p0, int64_t n, hipStream_t 
   A.n_part = (int32_t)n;
   A.dense_lo = dense_lo;
   if (!with_dense) A.n_kept_sent = 0;
+  if (W.sliced) {
+    // The whole plan by the persistent grid. `dense` is packed by the waves that leave the queue
+    // (the default), or by densify_kernel behind (LDDL_PLAN_SLICE_DENSE=0) or ahead of the
+    // planner (2): the one-shot launch's tail, which hides that work, no longer exists.
+    auto densify = [&]() {
+      if (A.n_kept_sent)
+        hipLaunchKernelGGL(densify_kernel, dim3((unsigned)((A.n_kept_sent + 255) / 256)), dim3(256), 0, st,
+                           A.ks_start, A.ks_len, A.kscan, A.n_kept_sent, A.ids, A.dense);
+    };
+    LDDL_HIP(hipMemsetAsync(W.sl_queue, 0, 4 * (4 + ((W.sl_ring_cap + 3) & ~(int64_t)3)), st));
+    if (W.sl_dense == 2) densify();
+    hipLaunchKernelGGL(planner_kernel(W), dim3((unsigned)W.sl_grid), dim3(64), kPlanLds, st, A);
+    if (W.sl_dense == 0) densify();
+    LDDL_HIP(hipGetLastError());
+    return 0;
+  }
   const unsigned grid = (unsigned)n + (A.n_kept_sent ? (unsigned)A.n_dense_wg : 0u);
   if (grid) hipLaunchKernelGGL(planner_kernel(W), dim3(grid), dim3(64), kPlanLds, st, A);
   LDDL_HIP(hipGetLastError());
@@ -2977,7 +3281,10 @@ static int plan_replay_unsplit(lddl_pairs* P, PlanWork& W, int attempt) {
     unsigned long long ctl[4];
     LDDL_HIP(hipMemcpyAsync(ctl, W.pool_ctl, 32, hipMemcpyDeviceToHost, st));
     LDDL_HIP(hipMemcpyAsync(&P->n_pairs, P->part_base + n_part, 8, hipMemcpyDeviceToHost, st));
+    unsigned sl_ctl[4] = {0, 0, 0, 0};
+    if (W.sliced) LDDL_HIP(hipMemcpyAsync(sl_ctl, W.sl_queue, 16, hipMemcpyDeviceToHost, st));
     LDDL_HIP(hipStreamSynchronize(st));
+    P->n_slices = sl_ctl[1];
     W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
     if (!prm->masking) break;
     if (!ctl[1]) {
@@ -3149,6 +3456,31 @@ static int report_plan_stamps(const PlanWork& W) {
     fprintf(stderr, " %.1f", (t[2 * q] - t0) / 1e5);
   }
   fprintf(stderr, "\n");
+  if (W.sliced) {  // the slices (one per ticket): how many waves were planning in every bin
+    const int64_t n_tk = n_part + W.sl_ring_cap;
+    std::vector<uint64_t> ts(2 * n_tk);
+    LDDL_HIP(hipMemcpyAsync(ts.data(), W.d_tls, 16 * n_tk, hipMemcpyDeviceToHost, st));
+    LDDL_HIP(hipStreamSynchronize(st));
+    std::vector<double> sl;
+    for (int64_t q = 0; q < n_tk; ++q)
+      if (ts[2 * q + 1]) sl.push_back((ts[2 * q + 1] - ts[2 * q]) / 1e5);
+    std::sort(sl.begin(), sl.end());
+    if (!sl.empty())
+      fprintf(stderr, "[timeline] %zu slices on %lld waves, slice ms min %.2f p50 %.2f p90 %.2f max %.2f\n",
+              sl.size(), (long long)W.sl_grid, sl[0], sl[sl.size() / 2], sl[sl.size() * 9 / 10], sl.back());
+    fprintf(stderr, "[timeline] active waves (slices) per %.2f ms bin:", span / nb);
+    for (int b = 0; b < nb; ++b) {
+      const uint64_t a = t0 + (t1 - t0) * b / nb, e = t0 + (t1 - t0) * (b + 1) / nb;
+      double act = 0;
+      for (int64_t q = 0; q < n_tk; ++q) {
+        if (!ts[2 * q + 1]) continue;
+        const uint64_t s0 = std::max(a, ts[2 * q]), s1 = std::min(e, ts[2 * q + 1]);
+        if (s1 > s0) act += (double)(s1 - s0);
+      }
+      fprintf(stderr, " %.0f", act / (double)(e - a));
+    }
+    fprintf(stderr, "\n");
+  }
   return 0;
 }
 #endif
@@ -3257,7 +3589,8 @@ static int plan_head_stage(lddl_pairs* P, const int64_t* d_sent_off, const int32
   if (W.prm->rng == LDDL_RNG_NATIVE) {
     if ((rc = plan_native(P, W))) return rc;
   } else {
-    if ((rc = plan_replay_setup(P, W)) || (rc = choose_split(W, &W.split))) return rc;
+    if ((rc = plan_replay_setup(P, W)) || (rc = choose_slice(P, W)) || (rc = choose_split(W, &W.split)))
+      return rc;
     if (!W.split) {
       if ((rc = plan_replay_unsplit(P, W, 0)) || (rc = finish_unsplit(P, W))) return rc;
     } else {
@@ -3363,10 +3696,10 @@ extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_p
                                     int64_t n_part, lddl_pairs** out, int64_t* head) {
   if (out) *out = nullptr;
   FyKnobs fy;
-  int64_t split_knob;
+  int64_t split_knob, slice_knob, waves_knob;
   int rc;
   if (!out) LDDL_FAIL(-1, "null argument");
-  if ((rc = check_plan_args(c, prm, &fy, &split_knob))) return rc;
+  if ((rc = check_plan_args(c, prm, &fy, &split_knob, &slice_knob, &waves_knob))) return rc;
   hipStream_t st = as_stream(stream);
   // until it is handed out, an error return drops the plan: its blocks go back on `st` (after
   // the tail launch, when one is in flight)
@@ -3380,7 +3713,8 @@ extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_p
   P->max_pred = max_predictions(prm);
   LDDL_HIP(hipEventCreate(&P->ev[0]));
   LDDL_HIP(hipEventCreate(&P->ev[1]));
-  P->work.reset(new PlanWork{c, &P->prm, d_ids, d_part_seed, n_sent, n_part, st, P->mem, fy, split_knob});
+  P->work.reset(new PlanWork{c, &P->prm, d_ids, d_part_seed, n_sent, n_part, st, P->mem, fy, split_knob,
+                              slice_knob, waves_knob});
   if ((rc = plan_head_stage(P.get(), d_sent_off, d_sent_len, d_doc_sent_off, n_doc, d_part_doc_off)))
     return rc;
   if (head) {
@@ -3396,6 +3730,7 @@ extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_p
       head[5] = plan_suggest_capacity(h.n_tokens, W.n_kept_tok, W.h_split_info[1]);
       head[6] = plan_suggest_capacity(h.n_masked, W.n_kept_tok, W.h_split_info[1]);
     }
+    head[7] = P->n_slices;
   }
   *out = P.release();
   return 0;

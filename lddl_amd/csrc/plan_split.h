@@ -1,7 +1,8 @@
-// The two host decisions of the split replay plan (pairs.hip): where the planner's partitions are
-// cut into a head and a tail range, and how large the caller's output buffers should be when only
-// the head's counts are known. (Host-only and free of the HIP runtime, so a CPU program can test
-// it: tests/plan_split_check.cpp.)
+// The host decisions of the replay plan's two large-batch forms (pairs.hip). The split plan:
+// where the planner's partitions are cut into a head and a tail range, and how large the
+// caller's output buffers should be when only the head's counts are known. The time-sliced plan:
+// whether to slice, the quantum and the hand-off ring's size. (Host-only and free of the HIP
+// runtime, so a CPU program can test it: tests/plan_split_check.cpp, tests/plan_slice_check.cpp.)
 #pragma once
 #include <cstdint>
 
@@ -35,6 +36,60 @@ inline int64_t plan_suggest_capacity(int64_t head_count, int64_t tok_all, int64_
   if (tok_head > 0 && tok_all > tok_head)
     v = (v * (unsigned __int128)(uint64_t)tok_all + (uint64_t)tok_head - 1) / (uint64_t)tok_head;
   v += v / 64 + 1024;
+  const unsigned __int128 lim = (unsigned __int128)INT64_MAX;
+  return (int64_t)(v > lim ? lim : v);
+}
+
+// ---- the time-sliced plan (pairs.hip, plan_replay_kernel's sliced mode) ----
+// A sliced plan is one range planned by persistent waves: a wave works on a partition for a
+// quantum of documents, parks its state and takes the next partition from a FIFO, so all the
+// partitions share all the wave slots instead of the last ones running alone.
+
+// Slices per partition of the automatic quantum (the partition's dup x documents / K). The
+// chains end together to within one slice, so shorter slices shorten the launch's ramp-down,
+// against ~K hand-offs per partition. (Measured on the 9,537-partition headline, partitions of
+// ~1,335 units, pair stage: K = 3: 152.5 ms, 5: 152.4, 10: 151.6, 20: 150.5;
+// profiles/r08_sliced_ab.txt.)
+constexpr int64_t kPlanSliceK = 20;
+
+// Whether the automatic mode slices at all (profiles/r08_sliced_ab.txt; the knob always can).
+constexpr bool kPlanSliceAuto = true;
+
+// Whether a one-range replay plan runs time-sliced.
+//   capacity: planner workgroups the device holds at once (0: unknown)
+//   knob:     LDDL_PLAN_SLICE: -1 automatic, 0 never, k > 0 always, with a quantum of k documents
+// Automatic: only when the partitions exceed the capacity (else every partition has a slot from
+// the start and there is nothing to share).
+inline bool plan_slice_on(int64_t n_part, int64_t capacity, int64_t knob) {
+  if (n_part <= 0 || knob == 0) return false;
+  if (knob > 0) return true;
+  return kPlanSliceAuto && capacity >= 2 && n_part > capacity;
+}
+
+// Documents (counted over the duplicate passes) a wave plans of a partition of `units` = dup x
+// documents before it yields: the knob's count, else 1/K of the partition, rounded up; >= 1.
+// (plan_replay_kernel computes the same per partition.)
+inline int64_t plan_slice_quantum(int64_t units, int64_t knob) {
+  if (knob > 0) return knob;
+  if (units <= 0) return 1;
+  return units / kPlanSliceK + (units % kPlanSliceK != 0);
+}
+
+// Entries of the hand-off ring: never below the hand-offs the quantum implies. A partition of u
+// units yields ceil(u / q) - 1 <= u / q times, so a forced quantum q gives at most
+// units_total / q in all; the automatic quantum at most K - 1 per partition (and never more than
+// one per unit). Plus 16 entries of margin; saturating at INT64_MAX.
+inline int64_t plan_slice_ring_entries(int64_t n_part, int64_t units_total, int64_t knob) {
+  if (n_part < 0) n_part = 0;
+  if (units_total < 0) units_total = 0;
+  unsigned __int128 v;
+  if (knob > 0) {
+    v = (unsigned __int128)((uint64_t)units_total / (uint64_t)knob);
+  } else {
+    v = (unsigned __int128)(uint64_t)n_part * (uint64_t)(kPlanSliceK - 1);
+    if (v > (unsigned __int128)(uint64_t)units_total) v = (uint64_t)units_total;
+  }
+  v += 16;
   const unsigned __int128 lim = (unsigned __int128)INT64_MAX;
   return (int64_t)(v > lim ? lim : v);
 }

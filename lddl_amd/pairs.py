@@ -114,11 +114,14 @@ def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_se
     do_whole_word_mask: the same pairs as whole_word=False, each with at most the per-token
     mode's number of masked positions, possibly none.
 
-    A large replay batch with static masking is planned in two partition ranges
-    (include/lddl_amd.h, lddl_pairs_plan_head): the first range's pairs are gathered, into
-    buffers sized from its counts, while the planner still works on the second.
+    A replay batch of more partitions than the device holds planner waves is planned
+    time-sliced in one range (LDDL_PLAN_SLICE, include/lddl_amd.h). With LDDL_PLAN_SPLIT forced,
+    or slicing switched off, a batch with static masking is planned in two partition ranges
+    (lddl_pairs_plan_head): the first range's pairs are gathered, into buffers sized from its
+    counts, while the planner still works on the second.
     (_capacity_scale: tests only, scales those sizes to force the regrow path; _trace: a dict
-    that receives which path ran.)
+    that receives which path ran, and 'slices': the hand-offs of a time-sliced plan,
+    LDDL_PLAN_SLICE.)
     """
     _check_whole_word(whole_word, masking, rng)
     dev = ctx.device
@@ -165,7 +168,7 @@ def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_se
             path = 'full'
         if _trace is not None:
             _trace.update(split=int(head[0]), head_pairs=int(head[1]),
-                          head_valid=int(head_valid.value), path=path)
+                          head_valid=int(head_valid.value), path=path, slices=int(head[7]))
         part_off = torch.empty(n_part + 1, dtype=torch.int64, device=dev)
         check(lib.lddl_pairs_part_offsets(h, st, _ptr(part_off)))
         ms = ctypes.c_float()
