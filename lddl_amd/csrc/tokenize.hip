@@ -263,9 +263,10 @@ struct Pcs {
 };
 
 // Diagnostic build: work counters of phase B (per lane; summed at the kernel's end).
+[[maybe_unused]] constexpr int kTokCounters = 12;  // 10: kQSlow lanes of the passes, 11: passes with at least one
 struct TokStats {
 #ifdef LDDL_STAMPS
-  uint64_t c[10];
+  uint64_t c[kTokCounters];
   __device__ void add(int i, uint64_t v) { c[i] += v; }
   // once per wave-level iteration: only the first active lane counts
   __device__ void wave(int i) {
@@ -640,10 +641,135 @@ __device__ int unit_pieces(const Tables& T, const uint32_t* bloom, const uint32_
   return wordpiece32(T, bloom, v, nb, ends, pc);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Non-ASCII ("slow") units from registers. unit_word's loop pays one dependent global load per
+// raw byte and three more per non-ASCII code point (UTF-8 tail, l1, pages) while the other lanes
+// of the phase-B pass wait: 45 % of phase B in the lookup launch
+// (profiles/r09_tok_phaseB_split_parent.txt). norm_regs takes a unit of <= 32 raw bytes
+// with one load32, decodes its non-ASCII code points from the registers (at most kSlowCps; more:
+// the loop), loads their l1 and pages entries with nothing else between, and only then walks the
+// bytes (ASCII through s_ascii in LDS; no global load in the walk but a kMulti entry's pool
+// bytes), writing the normalised word to the lane's LDS row as the loop does. Same rules as
+// utf8_next / unit_word's loop, byte for byte.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSlowCps = 4;
+constexpr uint64_t k80 = 0x8080808080808080ull;
+
+__device__ inline uint32_t byte_at(const B32& v, int j) {  // j in 0..31
+  const uint64_t w = j < 8 ? v.w0 : j < 16 ? v.w1 : j < 24 ? v.w2 : v.w3;
+  return (uint32_t)(w >> (8 * (j & 7))) & 0xFFu;
+}
+
+// bit i of the result: bit 7 of byte i of t (t has no other bits set). The product's terms
+// never share a bit position, so nothing carries.
+__device__ inline uint32_t top_bits(uint64_t t) {
+  return (uint32_t)(((t >> 7) * 0x0102040810204080ull) >> 56);
+}
+__device__ inline uint32_t top_bits32(const B32& t) {
+  return top_bits(t.w0) | top_bits(t.w1) << 8 | top_bits(t.w2) << 16 | top_bits(t.w3) << 24;
+}
+
+// utf8_next over raw bytes held in registers (end <= 32)
+__device__ inline uint32_t utf8_next_regs(const B32& v, int end, int& i) {
+  const uint32_t c = byte_at(v, i);
+  if (c < 0x80) { ++i; return c; }
+  const int len = c >= 0xF0 ? 4 : c >= 0xE0 ? 3 : c >= 0xC0 ? 2 : 1;
+  if (len == 1 || i + len > end) { ++i; return 0xFFFD; }
+  uint32_t cp = c & (0x7Fu >> len);
+  for (int k = 1; k < len; ++k) {
+    const uint32_t d = byte_at(v, i + k);
+    if ((d & 0xC0) != 0x80) { ++i; return 0xFFFD; }
+    cp = (cp << 6) | (d & 0x3F);
+  }
+  i += len;
+  return cp;
+}
+
+// Returns the normalised bytes written to w, -1: more than kNorm, -2: more than kSlowCps non-ASCII
+// code points (nothing done).
+__device__ __forceinline__ int norm_regs(const Tables& T, const uint32_t* s_ascii, const uint8_t* __restrict__ text,
+                         int64_t n_bytes, int64_t start, int len, uint8_t* w) {
+  const B32 raw = load32(text, n_bytes, start);
+  const uint32_t in_unit = len >= 32 ? ~0u : (1u << len) - 1u;
+  // bit j: raw byte j is not ASCII. The walk below meets such a byte only where a code point
+  // starts (a lead, a lone continuation, 0xFF), in the order in which they are decoded here.
+  const uint32_t hi = top_bits32(B32{raw.w0 & k80, raw.w1 & k80, raw.w2 & k80, raw.w3 & k80}) & in_unit;
+  uint32_t cp[kSlowCps], ent[kSlowCps], advs = 0, rest = hi;
+#pragma unroll
+  for (int k = 0; k < kSlowCps; ++k) {
+    cp[k] = 0;
+    if (rest) {
+      const int j = __builtin_ctz(rest);
+      int i = j;
+      cp[k] = utf8_next_regs(raw, len, i);
+      advs |= (uint32_t)(i - j) << (3 * k);
+      rest = i >= 32 ? 0u : rest & (~0u << i);
+    }
+  }
+  if (rest) return -2;
+#ifdef LDDL_SLOW_BATCH
+  {
+    // A/B variant: the l1 loads of all slots together, then the pages loads (an unused
+    // slot loads entry 0: no branch around the loads; the empty asm makes every pages load depend
+    // on every l1 load). Two round trips however many code points, but 2 more spilled VGPRs
+    // in the lookup kernel than the parent has.
+    uint32_t page[kSlowCps];
+#pragma unroll
+    for (int k = 0; k < kSlowCps; ++k) page[k] = T.l1[cp[k] > 0x10FFFFu ? 0u : cp[k] >> 8];
+    static_assert(kSlowCps == 4, "the dependency below names four");
+    asm volatile("" : "+v"(page[0]), "+v"(page[1]), "+v"(page[2]), "+v"(page[3]));
+#pragma unroll
+    for (int k = 0; k < kSlowCps; ++k) ent[k] = T.pages[page[k] * 256u + (cp[k] & 255u)];
+#pragma unroll
+    for (int k = 0; k < kSlowCps; ++k)
+      if (cp[k] > 0x10FFFFu) ent[k] = kDrop << 30;
+  }
+#else
+  // the table entries of the decoded code points: two dependent loads each, before the walk
+#pragma unroll
+  for (int k = 0; k < kSlowCps; ++k) {
+    ent[k] = 0;
+    if (advs >> (3 * k)) ent[k] = tab_entry(T, cp[k]);
+  }
+#endif
+  int nb = 0;
+  for (int j = 0; j < len;) {
+    uint32_t c, e;
+    if (!((hi >> j) & 1u)) {
+      c = byte_at(raw, j);
+      e = s_ascii[c];
+      ++j;
+    } else {  // the next decoded code point
+      c = cp[0];
+      e = ent[0];
+      j += (int)(advs & 7u);
+      advs >>= 3;
+#pragma unroll
+      for (int k = 0; k + 1 < kSlowCps; ++k) cp[k] = cp[k + 1], ent[k] = ent[k + 1];
+    }
+    if ((e >> 30) == kDrop) continue;
+    if (!(e & kIdent) && (e & kMulti)) {  // (rare: the pool bytes are loaded one after another)
+      const uint8_t* p = T.pool + (e & 0xFFFFFFu);
+      const int olen = p[0];
+      if (nb + olen > kNorm) return -1;
+      for (int q = 0; q < olen; ++q) w[nb + q] = p[2 + q];
+      nb += olen;
+    } else {
+      const uint32_t o = (e & kIdent) ? c : e & 0x1FFFFFu;
+      const int olen = o < 0x80 ? 1 : o < 0x800 ? 2 : o < 0x10000 ? 3 : 4;
+      if (nb + olen > kNorm) return -1;
+      put_utf8(w + nb, o);
+      nb += olen;
+    }
+  }
+  return nb;
+}
+
 // The normalised word of a word / isolated-char unit in registers (<= 32 bytes) and the byte
 // positions where a piece may end. status: 0 ok, 1 empty (every char dropped: 0 pieces), -1 the
 // unit needs the lane kernel (> kNorm normalised bytes). ASCII units are loaded straight from the
-// text (SWAR lowercase); others are normalised through the lane's LDS row `w` first.
+// text (SWAR lowercase); others are normalised through the lane's LDS row `w` first, from
+// registers where norm_regs takes the unit and `regs` allows it, else byte by byte from the text.
 struct UnitWord {
   B32 v;
   int nb;
@@ -651,8 +777,9 @@ struct UnitWord {
   int status;
 };
 
-__device__ UnitWord unit_word(const Tables& T, const uint32_t* s_ascii, const uint8_t* __restrict__ text,
-                              int64_t n_bytes, int64_t start, int len, bool unit_slow, uint8_t* w) {
+__device__ __forceinline__ UnitWord unit_word(const Tables& T, const uint32_t* s_ascii, const uint8_t* __restrict__ text,
+                              int64_t n_bytes, int64_t start, int len, bool unit_slow, uint8_t* w,
+                              bool regs) {
   UnitWord u;
   u.status = 0;
   if (!unit_slow && len <= 32 && T.ascii_mode != 0) {
@@ -663,47 +790,51 @@ __device__ UnitWord unit_word(const Tables& T, const uint32_t* s_ascii, const ui
     u.ends = ~0ull;
     return u;
   }
-  int nb = 0;
-  int64_t j = start;
-  const int64_t je = start + len;
-  while (j < je) {
-    const uint32_t b0 = text[j];
-    uint32_t cp, e;
-    if (b0 < 0x80) {
-      cp = b0;
-      e = s_ascii[b0];
-      ++j;
-    } else {
-      cp = utf8_next(text, je, j);
-      e = tab_entry(T, cp);
+  int nb = -2;
+  if (regs && len <= 32 && T.ascii_mode != 0) nb = norm_regs(T, s_ascii, text, n_bytes, start, len, w);
+  if (nb == -2) {  // byte by byte from the text
+    nb = 0;
+    int64_t j = start;
+    const int64_t je = start + len;
+    while (j < je) {
+      const uint32_t b0 = text[j];
+      uint32_t cp, e;
+      if (b0 < 0x80) {
+        cp = b0;
+        e = s_ascii[b0];
+        ++j;
+      } else {
+        cp = utf8_next(text, je, j);
+        e = tab_entry(T, cp);
+      }
+      if ((e >> 30) == kDrop) continue;
+      uint8_t ob[12];
+      int olen;
+      if (e & kIdent) olen = put_utf8(ob, cp);
+      else if (e & kMulti) {
+        const uint8_t* p = T.pool + (e & 0xFFFFFFu);
+        olen = p[0];
+        for (int q = 0; q < olen; ++q) ob[q] = p[2 + q];
+      } else olen = put_utf8(ob, e & 0x1FFFFFu);
+      if (nb + olen > kNorm) {
+        nb = -1;
+        break;
+      }
+      for (int q = 0; q < olen; ++q) w[nb + q] = ob[q];
+      nb += olen;
     }
-    if ((e >> 30) == kDrop) continue;
-    uint8_t ob[12];
-    int olen;
-    if (e & kIdent) olen = put_utf8(ob, cp);
-    else if (e & kMulti) {
-      const uint8_t* p = T.pool + (e & 0xFFFFFFu);
-      olen = p[0];
-      for (int q = 0; q < olen; ++q) ob[q] = p[2 + q];
-    } else olen = put_utf8(ob, e & 0x1FFFFFu);
-    if (nb + olen > kNorm) {
-      u.status = -1;
-      return u;
-    }
-    for (int q = 0; q < olen; ++q) w[nb + q] = ob[q];
-    nb += olen;
   }
   u.nb = nb;
-  if (nb == 0) {
-    u.status = 1;
+  if (nb <= 0) {
+    u.status = nb < 0 ? -1 : 1;
     return u;
   }
-  uint64_t ends = 1ull << nb;
-  for (int e = 1; e < nb; ++e)
-    if ((w[e] & 0xC0) != 0x80) ends |= 1ull << e;
-  u.ends = ends;
   const uint64_t* w8 = reinterpret_cast<const uint64_t*>(w);
   u.v = B32{w8[0], w8[1], w8[2], w8[3]};
+  // a piece may end before every byte that does not continue a character (10xxxxxx), and at nb
+  const uint32_t cont = top_bits32(B32{u.v.w0 & ~(u.v.w0 << 1) & k80, u.v.w1 & ~(u.v.w1 << 1) & k80,
+                                       u.v.w2 & ~(u.v.w2 << 1) & k80, u.v.w3 & ~(u.v.w3 << 1) & k80});
+  u.ends = ((uint64_t)(~cont & ~1u) & ((1ull << nb) - 1ull)) | 1ull << nb;
   return u;
 }
 
@@ -833,6 +964,9 @@ constexpr int kChunk = 128;  // consecutive sentences claimed at a time
 static_assert((kChunk & (kChunk - 1)) == 0, "binary search over the chunk's sentences");
 using HIdx = std::conditional_t<(kSF > 256), uint16_t, uint8_t>;
 constexpr int32_t kHardBit = INT32_MIN;  // q_res: pieces are in column (res & 63) of pcs
+// q_npc of a hard unit between phase A and its phase-B pass: phase A's note
+constexpr uint32_t kRowMiss = 1u;   // probed at full length in phase A, not a single piece
+constexpr uint32_t kRowValid = 2u;  // its word is in the unit's phase-B row (32 B at pcs byte 32 k)
 // q_s entry: chunk-relative start byte (bits 0..27) | kind (28..30: 0 word / isolated char,
 // 2 + k literal special k) | kQSlow (the unit holds a byte the register fast path cannot take)
 constexpr int32_t kQPos = (1 << 28) - 1;
@@ -864,17 +998,36 @@ static_assert(kPcs * 64 * 4 >= 64 * kNorm, "normalised-word rows must fit the pi
 __device__ unsigned long long* g_tok_tl;  // diagnostic build: [wave][2] s_memrealtime start / end
 // diagnostic build: shader cycles per region, summed over waves (kTokRegions entries)
 __device__ unsigned long long* g_tok_reg;
-constexpr int kTokRegions = 6;  // 0 banks, 1 phase A, 2 phase B, 3 place, 4 queue shift, 5 chunk
+// 0 banks, 1 phase A, 2 phase B (reported as the sum of its sub-regions), 3 place, 4 queue shift,
+// 5 chunk; phase B's sub-regions: 6 B0 word fetch and normalise, 7 B1 memo load / compare /
+// unpack, 8 B2 greedy match of the misses, 9 B3 the rest of the pass
+constexpr int kTokRegions = 10;
+constexpr int kTokDiag = kTokRegions + kTokCounters;  // one launch's slice of g_tok_reg
+// the launches of one call report separately: slice 0 the memo-build (or only) launch, slice 1
+// the memo-lookup launch
+constexpr int kTokSlices = 2;
+constexpr int kTokTlWgs = 1024;  // workgroups per slice of g_tok_tl (stamps_begin checks the grid)
 #define TOK_STAMP(r)                                                     \
   do {                                                                   \
     const unsigned long long _now = __builtin_amdgcn_s_memtime();       \
     reg_acc[r] += _now - reg_last;                                       \
     reg_last = _now;                                                     \
   } while (0)
+// a stamp inside phase B's block of the lanes that hold a word: the diagnostic build ends the
+// block, stamps where the wave is whole again, and opens it anew; the product keeps one block
+// (closing it after the memo lookup or after the greedy match costs 4 more spilled VGPRs,
+// DESIGN §4)
+#define TOK_STAMP_SPLIT(r) \
+  }                        \
+  }                        \
+  TOK_STAMP(r);            \
+  if (lane < hn) {         \
+    if (uw.status == 0) {
 #else
 #define TOK_STAMP(r) \
   do {               \
   } while (0)
+#define TOK_STAMP_SPLIT(r)
 #endif
 
 template <int kMemo>  // kMemoOff / kMemoBuild / kMemoLookup (word memo above)
@@ -882,7 +1035,7 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
     Tables T_arg, const uint8_t* __restrict__ text, int64_t n_bytes, const int64_t* __restrict__ sent_off,
     int64_t n_sent, int32_t max_pieces, int32_t* __restrict__ ids, int32_t* __restrict__ sent_len_arg,
     int32_t* __restrict__ fb_list_arg, uint32_t* __restrict__ fb_n_arg, int32_t* __restrict__ chunk_ctr_arg,
-    WordMemo M) {
+    WordMemo M, int32_t slow_loop_arg) {
   __shared__ uint32_t s_ascii[128];
   __shared__ uint8_t s_cls[256];
   __shared__ uint32_t s_bloom[kBloomWords];
@@ -892,8 +1045,10 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
   __shared__ Tables s_T;
   // (and the per-chunk / rare output pointers, for the same reason)
   __shared__ int32_t* s_cold[4];
+  __shared__ int32_t s_slow_loop;  // LDDL_TOKENIZE_SLOW=loop: slow units take unit_word's loop
   if (threadIdx.x == 0) {
     s_T = T_arg;
+    s_slow_loop = slow_loop_arg;
     s_cold[0] = sent_len_arg;
     s_cold[1] = fb_list_arg;
     s_cold[2] = reinterpret_cast<int32_t*>(fb_n_arg);
@@ -904,10 +1059,10 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
   int32_t* const volatile* cold = s_cold;  // read where used (not hoisted into registers)
 #ifdef LDDL_STAMPS
   const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-  unsigned long long reg_acc[kTokRegions] = {0, 0, 0, 0, 0, 0};
+  unsigned long long reg_acc[kTokRegions] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long reg_last = __builtin_amdgcn_s_memtime();
   TokStats tstat;
-  for (int q = 0; q < 10; ++q) tstat.c[q] = 0;
+  for (int q = 0; q < kTokCounters; ++q) tstat.c[q] = 0;
   TokStats* tsp = &tstat;
 #else
   TokStats* tsp = nullptr;
@@ -1083,6 +1238,9 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
             if (hardr[r]) {
               const int k = nh + (int)popc_below(H);
               W.h_idx[k] = (HIdx)u;
+              // phase B learns from q_npc[u] (its own until phase B writes the piece count) what
+              // phase A did with the unit, and so whether row k holds a word
+              W.q_npc[u] = (uint8_t)(!elig[r] ? 0u : k < 64 ? kRowMiss | kRowValid : kRowMiss);
               // a probed word that missed: its (lowercased) bytes go to phase-B row k, so the
               // first phase-B pass reads them from LDS instead of loading the text again
               if (elig[r] && k < 64) {
@@ -1120,8 +1278,15 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
             st = qs & kQPos;
             const int len = W.q_e[u] - st + 1;
             const bool slow = qs < 0;
-            known_miss = !slow && T.ascii_mode != 0 && len <= T.max_piece_bytes && len <= 32;
-            if (h0 == 0 && known_miss) {  // phase A left the word in this lane's row
+            // phase A's note for this unit (kRowMiss: it probed the whole word and missed;
+            // kRowValid: it also left the word in row h0 + lane)
+            const uint32_t note = W.q_npc[u];
+            known_miss = (note & kRowMiss) != 0;
+            if (tsp) {
+              tsp->add(10, slow);
+              if (ballot(slow)) tsp->wave(11);
+            }
+            if (note & kRowValid) {
               const uint4* row = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(W.pcs) + 32 * lane);
               const uint4 r0 = row[0], r1 = row[1];
               uw.v = B32{r0.x | (uint64_t)r0.y << 32, r0.z | (uint64_t)r0.w << 32,
@@ -1131,49 +1296,55 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
               uw.status = 0;
             } else {
               uw = unit_word(T, s_ascii, text, n_bytes, A + st, len, slow,
-                             reinterpret_cast<uint8_t*>(W.pcs) + 32 * lane);
+                             reinterpret_cast<uint8_t*>(W.pcs) + 32 * lane, !s_slow_loop);
             }
           }
           wave_sync();  // every normalised word is in registers: the rows become piece columns
+          TOK_STAMP(6);
           int npc = 0;
+          bool hit = false;
+          Pcs pc{W.pcs + lane};
           if (lane < hn) {
-            Pcs pc{W.pcs + lane};
             if (uw.status == 0) {
-              if constexpr (kMemo == kMemoOff) {
-                npc = wordpiece32(T, s_bloom, uw.v, uw.nb, uw.ends, pc, known_miss, tsp);
-              } else {
-                const B32 key = memo_key(uw.v, uw.nb);
-                uint4* e = M.tab + 4 * (size_t)(memo_slot(key, uw.nb) & M.mask);
-                bool hit = false;
-                if constexpr (kMemo == kMemoLookup) {
-                  const uint4 k0 = e[0], k1 = e[1], pz = e[2];
-                  const uint32_t meta = e[3].x;
-                  hit = (meta & kMemoReady) && (int)(meta & 0xFFu) == uw.nb &&
-                        ((k0.x | (uint64_t)k0.y << 32) ^ key.w0 | (k0.z | (uint64_t)k0.w << 32) ^ key.w1 |
-                         (k1.x | (uint64_t)k1.y << 32) ^ key.w2 | (k1.z | (uint64_t)k1.w << 32) ^ key.w3) == 0;
-                  if (hit) {
-                    npc = (int)((meta >> 8) & 0xFu);
-                    const uint32_t pw[4] = {pz.x, pz.y, pz.z, pz.w};
+              if constexpr (kMemo != kMemoOff) {
+                // the memo key is the word with its bytes past nb cleared (don't-care bytes to
+                // every later use, so the word's own registers hold it)
+                uw.v = memo_key(uw.v, uw.nb);
+              }
+              if constexpr (kMemo == kMemoLookup) {
+                const B32& key = uw.v;
+                const uint4* e = M.tab + 4 * (size_t)(memo_slot(key, uw.nb) & M.mask);
+                const uint4 k0 = e[0], k1 = e[1], pz = e[2];
+                const uint32_t meta = e[3].x;
+                hit = (meta & kMemoReady) && (int)(meta & 0xFFu) == uw.nb &&
+                      (((k0.x | (uint64_t)k0.y << 32) ^ key.w0) | ((k0.z | (uint64_t)k0.w << 32) ^ key.w1) |
+                       ((k1.x | (uint64_t)k1.y << 32) ^ key.w2) | ((k1.z | (uint64_t)k1.w << 32) ^ key.w3)) == 0;
+                if (hit) {
+                  npc = (int)((meta >> 8) & 0xFu);
+                  const uint32_t pw[4] = {pz.x, pz.y, pz.z, pz.w};
 #pragma unroll
-                    for (int q = 0; q < kPcs; ++q)
-                      if (q < npc) pc.put(q, (int32_t)((pw[q >> 1] >> (16 * (q & 1))) & 0xFFFFu));
-                  }
+                  for (int q = 0; q < kPcs; ++q)
+                    if (q < npc) pc.put(q, (int32_t)((pw[q >> 1] >> (16 * (q & 1))) & 0xFFFFu));
                 }
-                if (!hit) npc = wordpiece32(T, s_bloom, uw.v, uw.nb, uw.ends, pc, known_miss, tsp);
-                if constexpr (kMemo == kMemoBuild) {
-                  // first writer of the slot in this call claims it; no lane of this launch reads
-                  if (npc >= 1 && atomicCAS(&e[3].x, 0u, kMemoClaim) == 0u) {
-                    uint32_t pw[4] = {0u, 0u, 0u, 0u};
+              }
+              TOK_STAMP_SPLIT(7);
+              if (!hit) npc = wordpiece32(T, s_bloom, uw.v, uw.nb, uw.ends, pc, known_miss, tsp);
+              TOK_STAMP_SPLIT(8);
+              if constexpr (kMemo == kMemoBuild) {
+                // first writer of the slot in this call claims it; no lane of this launch reads
+                const B32& key = uw.v;
+                uint4* e = M.tab + 4 * (size_t)(memo_slot(key, uw.nb) & M.mask);
+                if (npc >= 1 && atomicCAS(&e[3].x, 0u, kMemoClaim) == 0u) {
+                  uint32_t pw[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-                    for (int q = 0; q < kPcs; ++q)
-                      if (q < npc) pw[q >> 1] |= ((uint32_t)pc.get(q) & 0xFFFFu) << (16 * (q & 1));
-                    e[0] = make_uint4((uint32_t)key.w0, (uint32_t)(key.w0 >> 32), (uint32_t)key.w1,
-                                      (uint32_t)(key.w1 >> 32));
-                    e[1] = make_uint4((uint32_t)key.w2, (uint32_t)(key.w2 >> 32), (uint32_t)key.w3,
-                                      (uint32_t)(key.w3 >> 32));
-                    e[2] = make_uint4(pw[0], pw[1], pw[2], pw[3]);
-                    e[3].x = kMemoReady | (uint32_t)uw.nb | (uint32_t)npc << 8;
-                  }
+                  for (int q = 0; q < kPcs; ++q)
+                    if (q < npc) pw[q >> 1] |= ((uint32_t)pc.get(q) & 0xFFFFu) << (16 * (q & 1));
+                  e[0] = make_uint4((uint32_t)key.w0, (uint32_t)(key.w0 >> 32), (uint32_t)key.w1,
+                                    (uint32_t)(key.w1 >> 32));
+                  e[1] = make_uint4((uint32_t)key.w2, (uint32_t)(key.w2 >> 32), (uint32_t)key.w3,
+                                    (uint32_t)(key.w3 >> 32));
+                  e[2] = make_uint4(pw[0], pw[1], pw[2], pw[3]);
+                  e[3].x = kMemoReady | (uint32_t)uw.nb | (uint32_t)npc << 8;
                 }
               }
             } else if (uw.status < 0) {
@@ -1188,7 +1359,7 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
           }
           wave_sync();
           const int lim = h0 + 64 < nh ? (int)W.h_idx[h0 + 64] : m;
-          TOK_STAMP(2);
+          TOK_STAMP(9);
           place(placed, lim);
           placed = lim;
           TOK_STAMP(3);
@@ -1368,17 +1539,19 @@ __global__ void __launch_bounds__(64 * kBW, 1) tokenize_batch_kernel(
     c0 = nc < n_sent32 ? nc : n_sent32;
   }
 #ifdef LDDL_STAMPS
+  constexpr int slice = kMemo == kMemoLookup ? 1 : 0;
   if (lane == 0 && g_tok_tl) {
-    const int64_t wv = (int64_t)blockIdx.x * kBW + (threadIdx.x >> 6);
+    const int64_t wv = ((int64_t)slice * kTokTlWgs + blockIdx.x) * kBW + (threadIdx.x >> 6);
     g_tok_tl[2 * wv] = rt0;
     g_tok_tl[2 * wv + 1] = __builtin_amdgcn_s_memrealtime();
   }
-  if (lane == 0 && g_tok_reg)
-    for (int r = 0; r < kTokRegions; ++r) atomicAdd(g_tok_reg + r, reg_acc[r]);
-  if (g_tok_reg)
-    for (int q = 0; q < 10; ++q) {
+  unsigned long long* const reg = g_tok_reg ? g_tok_reg + slice * kTokDiag : nullptr;
+  if (lane == 0 && reg)
+    for (int r = 0; r < kTokRegions; ++r) atomicAdd(reg + r, reg_acc[r]);
+  if (reg)
+    for (int q = 0; q < kTokCounters; ++q) {
       const uint64_t v = wave_sum(tstat.c[q]);
-      if (lane == 0) atomicAdd(g_tok_reg + kTokRegions + q, (unsigned long long)v);
+      if (lane == 0) atomicAdd(reg + kTokRegions + q, (unsigned long long)v);
     }
 #endif
 }
@@ -1405,6 +1578,8 @@ struct TokCall {
   int32_t* chunk_ctr = nullptr;  // the batch kernel's chunk counter (after the list)
   int64_t n_cu = 256;
   int64_t grid = 0;  // workgroups of the last streaming launch
+  int64_t grid_of[2] = {0, 0};  // the same per diagnostic slice (0: not launched)
+  int32_t slow_loop = 0;        // LDDL_TOKENIZE_SLOW=loop
 };
 
 // The lane kernel over sentences [s0, s0 + n): those on the fallback list, or all of them
@@ -1441,6 +1616,7 @@ static int batch_pass(TokCall& T, int64_t grid_max, int64_t s0, int64_t n, int m
   // tests: a smaller grid makes small inputs take the dynamic chunk claims
   if (const char* g = getenv("LDDL_TOKENIZE_GRID")) grid = std::max<int64_t>(1, std::min<int64_t>(grid, atoll(g)));
   T.grid = grid;
+  T.grid_of[memo == kMemoLookup ? 1 : 0] = grid;
   // the first grid x kBW chunks are taken statically (chunk w by wave w)
   const int64_t first = std::min<int64_t>(grid * kBW * kChunk, (int64_t)INT32_MAX);
   LDDL_HIP(hipMemsetAsync(T.fb, 0, sizeof(int32_t) * kFbHead, T.st));
@@ -1453,27 +1629,32 @@ static int batch_pass(TokCall& T, int64_t grid_max, int64_t s0, int64_t n, int m
   int32_t* fl = T.fb + kFbHead;
   uint32_t* fn = reinterpret_cast<uint32_t*>(T.fb);
   void* args[] = {&T.c->tab, (void*)&T.d_text, &T.n_bytes, (void*)&so, &n, &T.max_pieces, &T.d_ids, &sl,
-                  &fl, &fn, &T.chunk_ctr, &M};
+                  &fl, &fn, &T.chunk_ctr, &M, &T.slow_loop};
   LDDL_HIP(hipLaunchKernel(kfn, dim3((unsigned)grid), dim3(64 * kBW), args, 0, T.st));
   return launch_lane(T, s0, n, T.n_cu * 2, false);
 }
 
 #ifdef LDDL_STAMPS
-// diagnostic build: the streaming kernel's wave timeline (tl) and region counters (rg)
+// diagnostic build: the streaming kernel's wave timelines (tl) and region counters (rg), one
+// slice per launch of the call
 static int stamps_begin(ArenaScope& diag, const TokCall& T, int64_t grid_max, unsigned long long** tl,
                         unsigned long long** rg) {
+  if (grid_max > kTokTlWgs) LDDL_FAIL(-1, "diagnostic build: %lld workgroups exceed kTokTlWgs", (long long)grid_max);
+  const size_t n_tl = (size_t)2 * kTokSlices * kTokTlWgs * kBW, n_rg = (size_t)kTokSlices * kTokDiag;
   int rc;
-  if ((rc = diag.take(tl, 2 * grid_max * kBW)) || (rc = diag.take(rg, kTokRegions + 10))) return rc;
-  LDDL_HIP(hipMemsetAsync(*tl, 0, 16 * grid_max * kBW, T.st));
+  if ((rc = diag.take(tl, n_tl)) || (rc = diag.take(rg, n_rg))) return rc;
+  LDDL_HIP(hipMemsetAsync(*tl, 0, 8 * n_tl, T.st));
   LDDL_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tok_tl), tl, sizeof(*tl), 0, hipMemcpyHostToDevice, T.st));
-  LDDL_HIP(hipMemsetAsync(*rg, 0, 8 * (kTokRegions + 10), T.st));
+  LDDL_HIP(hipMemsetAsync(*rg, 0, 8 * n_rg, T.st));
   LDDL_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tok_reg), rg, sizeof(*rg), 0, hipMemcpyHostToDevice, T.st));
   return 0;
 }
 
-static int report_tok_stamps(const TokCall& T, const unsigned long long* tl, const unsigned long long* rg) {
+// one launch's slice: `label` names it in every line
+static int report_tok_slice(const TokCall& T, const char* label, int64_t grid, const unsigned long long* tl,
+                            const unsigned long long* rg) {
   // wave timeline (100 MHz real-time clock)
-  const int64_t nw = T.grid * kBW;
+  const int64_t nw = grid * kBW;
   std::vector<unsigned long long> t(2 * nw);
   LDDL_HIP(hipMemcpyAsync(t.data(), tl, 16 * nw, hipMemcpyDeviceToHost, T.st));
   LDDL_HIP(hipStreamSynchronize(T.st));
@@ -1486,10 +1667,10 @@ static int report_tok_stamps(const TokCall& T, const unsigned long long* tl, con
   for (int64_t q = 0; q < nw; ++q) e[q] = (t[2 * q + 1] - t0) / 1e5;
   std::sort(e.begin(), e.end());
   const double span = (t1 - t0) / 1e5;
-  fprintf(stderr, "[tok timeline] span %.2f ms, wave end ms: min %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f\n",
-          span, e[0], e[nw / 10], e[nw / 2], e[nw * 9 / 10], e[nw - 1]);
+  fprintf(stderr, "[tok %s timeline] span %.2f ms, wave end ms: min %.2f p10 %.2f p50 %.2f p90 %.2f max %.2f\n",
+          label, span, e[0], e[nw / 10], e[nw / 2], e[nw * 9 / 10], e[nw - 1]);
   const int nb = 40;
-  fprintf(stderr, "[tok timeline] waves alive per %.2f ms bin:", span / nb);
+  fprintf(stderr, "[tok %s timeline] waves alive per %.2f ms bin:", label, span / nb);
   for (int b = 0; b < nb; ++b) {
     const double te = span * (b + 0.5) / nb;
     int64_t alive = 0;
@@ -1497,22 +1678,41 @@ static int report_tok_stamps(const TokCall& T, const unsigned long long* tl, con
     fprintf(stderr, " %lld", (long long)alive);
   }
   fprintf(stderr, "\n");
-  unsigned long long r[kTokRegions + 10];
+  unsigned long long r[kTokDiag];
   LDDL_HIP(hipMemcpy(r, rg, sizeof r, hipMemcpyDeviceToHost));
   const unsigned long long* k = r + kTokRegions;
   fprintf(stderr,
-          "[tok phaseB] flushes %llu units %llu | passes %llu lanes/pass %.1f | piece-steps: wave %llu "
+          "[tok %s phaseB] flushes %llu units %llu | passes %llu lanes/pass %.1f | piece-steps: wave %llu "
           "lane %llu (lane util %.2f) | bloom iters: wave %llu lane-useful %llu (util %.2f, per wave "
-          "step %.1f) | probe trips: wave %llu lane %llu (util %.2f)\n",
-          k[8], k[9], k[0], (double)k[1] / (k[0] ? k[0] : 1), k[2], k[3],
+          "step %.1f) | probe trips: wave %llu lane %llu (util %.2f) | slow lanes %llu (%.2f per pass), "
+          "passes with one %llu (%.1f%%)\n",
+          label, k[8], k[9], k[0], (double)k[1] / (k[0] ? k[0] : 1), k[2], k[3],
           (double)k[3] / (64.0 * (k[2] ? k[2] : 1)), k[4], k[5], (double)k[5] / (64.0 * (k[4] ? k[4] : 1)),
-          (double)k[4] / (k[2] ? k[2] : 1), k[6], k[7], (double)k[7] / (64.0 * (k[6] ? k[6] : 1)));
+          (double)k[4] / (k[2] ? k[2] : 1), k[6], k[7], (double)k[7] / (64.0 * (k[6] ? k[6] : 1)), k[10],
+          (double)k[10] / (k[0] ? k[0] : 1), k[11], 100.0 * k[11] / (k[0] ? k[0] : 1));
+  r[2] = r[6] + r[7] + r[8] + r[9];
   unsigned long long tot = 0;
-  for (int q = 0; q < kTokRegions; ++q) tot += r[q];
-  static const char* names[kTokRegions] = {"banks", "phaseA", "phaseB", "place", "qshift", "chunk"};
-  fprintf(stderr, "[tok regions] wave-cycle shares:");
-  for (int q = 0; q < kTokRegions; ++q) fprintf(stderr, " %s %.1f%%", names[q], 100.0 * r[q] / (tot ? tot : 1));
-  fprintf(stderr, "\n");
+  for (int q = 0; q < 6; ++q) tot += r[q];
+  static const char* names[kTokRegions] = {"banks", "phaseA", "phaseB", "place", "qshift", "chunk",
+                                           "B0 fetch+normalise", "B1 memo", "B2 greedy", "B3 rest"};
+  fprintf(stderr, "[tok %s regions] wave-cycle shares:", label);
+  for (int q = 0; q < 6; ++q) fprintf(stderr, " %s %.1f%%", names[q], 100.0 * r[q] / (tot ? tot : 1));
+  fprintf(stderr, "\n[tok %s phaseB split] share of phase B (of the kernel):", label);
+  for (int q = 6; q < kTokRegions; ++q)
+    fprintf(stderr, " %s %.1f%% (%.1f%%)", names[q], 100.0 * r[q] / (r[2] ? r[2] : 1), 100.0 * r[q] / (tot ? tot : 1));
+  fprintf(stderr, " | phase-B wave cycles per pass %.0f\n", (double)r[2] / (k[0] ? k[0] : 1));
+  return 0;
+}
+
+static int report_tok_stamps(const TokCall& T, const unsigned long long* tl, const unsigned long long* rg) {
+  static const char* labels[2][kTokSlices] = {{"single", ""}, {"build", "lookup"}};
+  const bool two = T.grid_of[1] > 0;
+  for (int s = 0; s < kTokSlices; ++s) {
+    if (!T.grid_of[s]) continue;
+    int rc = report_tok_slice(T, labels[two][s], T.grid_of[s], tl + (size_t)2 * s * kTokTlWgs * kBW,
+                              rg + (size_t)s * kTokDiag);
+    if (rc) return rc;
+  }
   return 0;
 }
 #endif
@@ -1535,6 +1735,13 @@ extern "C" int lddl_tokenize(lddl_ctx* c, void* stream, const uint8_t* d_text, i
   if (path && !strcmp(path, "lane")) return launch_lane(T, 0, n_sent, 65536, true);
   if (path && strcmp(path, "wave") && strcmp(path, "fused") && strcmp(path, "plain"))
     LDDL_FAIL(-1, "LDDL_TOKENIZE_PATH must be lane, wave, fused or plain (got %s)", path);
+  // A/B of the streaming kernel's non-ASCII units: "regs" (the default) normalises them from
+  // registers (unit_word_regs), "loop" byte by byte as before
+  if (const char* sl = getenv("LDDL_TOKENIZE_SLOW")) {
+    if (strcmp(sl, "regs") && strcmp(sl, "loop"))
+      LDDL_FAIL(-1, "LDDL_TOKENIZE_SLOW must be regs or loop (got %s)", sl);
+    T.slow_loop = !strcmp(sl, "loop");
+  }
   ArenaTmp fbb(&c->arena, st);
   LDDL_HIP(fbb.take(sizeof(int32_t) * (size_t)(n_sent + kFbHead + 1)));
   T.fb = fbb.as<int32_t>();
