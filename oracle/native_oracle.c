@@ -6,7 +6,7 @@
  * The algorithm is the reference's (create_pairs_from_document, lddl/dask/bert/pretrain.py:241-365;
  * _truncate_seq_pair 161-176; create_masked_lm_predictions 182-238; the partition shuffle 401),
  * drawing from Philox4x32-10 counter streams instead of one MT19937 per partition (the reference
- * seeds nothing), as lddl_amd/csrc/pairs.hip defines them:
+ * seeds nothing), as lddl_amd/csrc/pairs_native.hip defines them:
  *   walk of unit r = (duplicate dp, document dl), r = dp * nd + dl: stream (key, r, 1);
  *   masks of the k-th pair the planner made in the partition: sampling (key, k, 2), decisions
  *   (key, k, 4); partition order: a 4-round Feistel permutation keyed by mix64(key ^ 3);
