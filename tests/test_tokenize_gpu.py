@@ -143,6 +143,14 @@ def test_tokenize_path_unknown_raises(ctxs, monkeypatch):
         ctxs['uncased'].tokenize_host(text, np.asarray([0, len(text)], np.int64))
 
 
+@pytest.mark.parametrize('name,value', [('LDDL_TOKENIZE_GRID', 'abc'), ('LDDL_TOKENIZE_MEMO_SAMPLE', '-1')])
+def test_tokenize_number_knob_malformed_raises(ctxs, monkeypatch, name, value):
+    monkeypatch.setenv(name, value)
+    text = np.frombuffer(b'hello world', np.uint8)
+    with pytest.raises(Exception, match=name):
+        ctxs['uncased'].tokenize_host(text, np.asarray([0, len(text)], np.int64))
+
+
 def test_tokenize_long_and_empty_sentences(ctxs):
     """Sentences far beyond 512 pieces (early stop), runs of empty sentences (ring retirement),
     and one sentence per wave's stream position."""

@@ -1,7 +1,7 @@
 """The streaming tokenizer's non-ASCII ("slow") units against the oracle on a crafted corpus.
 
 Units of <= 32 raw bytes with at most four non-ASCII code points are normalised from registers
-(tokenize.hip, norm_regs); the others, and every one with LDDL_TOKENIZE_SLOW=loop, byte by byte
+(tokenize_dev.h, norm_regs); the others, and every one with LDDL_TOKENIZE_SLOW=loop, byte by byte
 from the text. The corpus below holds every shape either path treats differently, counted on the
 CPU before the GPU sees it, and runs with the knob in both positions through the plain kernel,
 both memo instantiations, a one-workgroup grid and a small max_pieces.
@@ -196,6 +196,8 @@ MODES = {
     'memo64': {'LDDL_TOKENIZE_MEMO_SAMPLE': '64'},
     'grid1': {'LDDL_TOKENIZE_GRID': '1'},
     'memo64_grid1': {'LDDL_TOKENIZE_MEMO_SAMPLE': '64', 'LDDL_TOKENIZE_GRID': '1'},
+    # the wave kernel takes its words from the same unit_word (always the byte-by-byte form)
+    'wave': {'LDDL_TOKENIZE_PATH': 'wave'},
 }
 
 

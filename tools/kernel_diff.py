@@ -7,7 +7,9 @@ Kernels are paired by demangled name with `(anonymous namespace)::` dropped, so 
 to another translation unit and its argument types to another namespace. Per kernel the table says
 whether the instruction text and the descriptor (the .amdhsa_kernel block and the kernel's
 metadata entry: registers, LDS, scratch, workgroup size, arguments) are identical once comments,
-trailing blanks and local label numbers are stripped. Exit status 1 on any difference, on a
+trailing blanks and local label numbers are stripped. The compiler numbers its private constants
+(.str, .str.N) per file, so a reference to one is compared by what the constant holds, not by its
+number: the same instructions over constants of different content are DIFFERENT. Exit status 1 on any difference, on a
 kernel that only one side has, and on a kernel that a side has more than once.
 """
 import re
@@ -15,6 +17,9 @@ import shutil
 import subprocess
 import sys
 
+# a compiler-generated private constant (.str, .str.N): a reference, and its definition's label
+PRIVATE = re.compile(r'(?<![\w.])\.str(\.\d+)?(?![\w.])')
+PRIVATE_DEF = re.compile(r'\.str(\.\d+)?:$')
 
 def kernels(path, out):
     """out[name] = list of (instruction text, descriptor) of the kernels in one assembly file"""
@@ -22,6 +27,12 @@ def kernels(path, out):
     text = subprocess.run([filt], input=open(path).read(), stdout=subprocess.PIPE, text=True,
                           check=True).stdout.replace('(anonymous namespace)::', '')
     lines = [re.sub(r'\.L([A-Za-z]+)\d+', r'.L\1', ln.split(';')[0].rstrip()) for ln in text.split('\n')]
+    # consts[symbol] = the data directives of a private constant, as written (label .. .size)
+    consts, raw = {}, text.split('\n')
+    for i, ln in enumerate(raw):
+        if PRIVATE_DEF.match(ln):
+            j = next(k for k in range(i + 1, len(raw)) if raw[k].startswith('\t.size'))
+            consts[ln[:-1]] = '\n'.join(raw[i + 1:j])
     meta = {}
     body = '\n'.join(lines)
     k0, k1 = body.find('amdhsa.kernels:'), body.find('amdhsa.target:')
@@ -38,6 +49,9 @@ def kernels(path, out):
         # (the section switches around the descriptor carry the mangled name)
         code = [x for x in lines[start + 1:d0] + lines[d1 + 1:end]
                 if x.strip() and not x.startswith(('\t.section', '\t.text'))]
+        # the compiler numbers its private constants per file: compare what each reference holds
+        refs = [m.group(0) for x in code for m in PRIVATE.finditer(x)]
+        code = [PRIVATE.sub('.str', x) for x in code] + ['.str = ' + consts.get(r, 'undefined') for r in refs]
         desc = [x for x in lines[d0 + 1:d1] if x.strip()] + [meta[name].rstrip()]
         out.setdefault(name, []).append(('\n'.join(code), '\n'.join(desc)))
 
