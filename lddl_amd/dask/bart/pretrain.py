@@ -33,7 +33,8 @@ import numpy as np
 
 from ...utils import expand_outdir_and_mkdir, parse_str_of_num_bytes
 from .. import readers
-from ..bert.pretrain import ASSETS, _greedy, _pad_name, _prefetch, punkt_params
+from ..bert.corpus import ASSETS, greedy, prefetch, punkt_params
+from ..bert.writers import pad_name
 
 
 def plan_partitions(args):
@@ -58,8 +59,8 @@ def plan_partitions(args):
 def iter_batches(args, blocks, pool):
     """GPU batches of whole partitions: yields ([partition numbers], text uint8, doc_off int64,
     part_doc_off int64); a document is one whole stripped line."""
-    for batch in _greedy(list(range(len(blocks))), lambda p: blocks[p].nbytes,
-                         args.gpu_batch_bytes):
+    for batch in greedy(list(range(len(blocks))), lambda p: blocks[p].nbytes,
+                        args.gpu_batch_bytes):
         parts = list(pool.map(lambda p: readers.read_block(blocks[p], as_bytes=True), batch))
         lines = [x for ls in parts for x in ls]
         text = np.frombuffer(b''.join(lines), np.uint8) if lines else np.zeros(0, np.uint8)
@@ -180,13 +181,13 @@ def main(args):
     from concurrent.futures import ThreadPoolExecutor
     rpool = ThreadPoolExecutor(max_workers=max(1, args.read_threads))
     wpool = ThreadPoolExecutor(max_workers=max(1, args.write_threads))
-    batches = _prefetch(iter_batches(args, blocks, rpool))  # reads while the device is set up
+    batches = prefetch(iter_batches(args, blocks, rpool))  # reads while the device is set up
     from ... import punkt
     from ...context import Context
     # (the context carries the tokenizer tables of the BERT path; BART uses its Punkt tables only)
     ctx = Context(os.path.join(ASSETS, 'vocab_synth_uncased_30522.txt'))
     punkt.set_params(ctx, punkt_params(args))
-    name = _pad_name(n_part)
+    name = pad_name(n_part)
     timer = _StageTimer()
     inflight = []  # write futures per batch: at most two batches of chunks in host memory
     n_files = 0

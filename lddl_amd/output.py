@@ -109,6 +109,31 @@ def render(ctx, pb, rows=None, bin_id=None):
     return render_device(ctx, pb, rows, bin_id).to_host()
 
 
+def _to_pinned(t, st, b0=None, b1=None):
+    """Device tensor `t`, or its elements [b0, b1), in a fresh pinned host tensor: an
+    asynchronous copy on `st`, which the caller has made the current stream. (An empty range
+    still allocates one element and copies nothing.)"""
+    src = t if b0 is None else t[b0:b1]
+    h = torch.empty(max(src.numel(), 1), dtype=t.dtype, pin_memory=True)[:src.numel()]
+    if src.numel():
+        h.copy_(src, non_blocking=True)
+    t.record_stream(st)
+    return h
+
+
+def _rendered(rows, byts, is_random_next, masking, bin_id):
+    """A Rendered over the host row columns `rows` and the four byte columns `byts` (dicts by
+    column name); is_random_next is the caller's bool array, bin_id its int64 one or None."""
+    rd = Rendered(rows['a_off'], byts['a_bytes'], rows['b_off'], byts['b_bytes'],
+                  is_random_next, rows['num_tokens'].view(np.uint16))
+    if masking:
+        rd.l_off, rd.l_bytes = rows['l_off'], byts['l_bytes']
+        rd.npy_off, rd.npy_bytes = rows['npy_off'], byts['npy_bytes']
+    if bin_id is not None:
+        rd.bin_id = bin_id
+    return rd
+
+
 @dataclass
 class DeviceRendered:
     """render()'s columns still in HBM (device tensors), with the stream event after which they
@@ -137,22 +162,15 @@ class DeviceRendered:
                 if _PAGEABLE:  # (A/B diagnostics) pageable host buffers
                     h = torch.empty(max(t.numel(), 1), dtype=t.dtype)[:t.numel()]
                     h.copy_(t)
+                    t.record_stream(st)
                 else:
-                    h = torch.empty(max(t.numel(), 1), dtype=t.dtype, pin_memory=True)[:t.numel()]
-                    h.copy_(t, non_blocking=True)
-                t.record_stream(st)
+                    h = _to_pinned(t, st)
                 out[k] = h
         st.synchronize()
         n = {k: (v.numpy() if v is not None else None) for k, v in out.items()}
-        rd = Rendered(n['a_off'], n['a_bytes'], n['b_off'], n['b_bytes'],
-                      n['is_rn'].astype(bool), n['num_tokens'].view(np.uint16))
-        if self.masking:
-            rd.l_off, rd.l_bytes = n['l_off'], n['l_bytes']
-            rd.npy_off, rd.npy_bytes = n['npy_off'], n['npy_bytes']
-        if n.get('bin_id') is not None:
-            rd.bin_id = n['bin_id'].astype(np.int64)
         self.cols = None
-        return rd
+        return _rendered(n, n, n['is_rn'].astype(bool), self.masking,
+                         None if n.get('bin_id') is None else n['bin_id'].astype(np.int64))
 
     _ROW_COLS = ('a_off', 'b_off', 'l_off', 'npy_off', 'is_rn', 'num_tokens', 'bin_id')
     _BYTE_COLS = (('a_off', 'a_bytes'), ('b_off', 'b_bytes'), ('l_off', 'l_bytes'),
@@ -177,10 +195,7 @@ class DeviceRendered:
                 t = cols.get(k)
                 if t is None:
                     continue
-                h = torch.empty(max(t.numel(), 1), dtype=t.dtype, pin_memory=True)[:t.numel()]
-                h.copy_(t, non_blocking=True)
-                t.record_stream(st)
-                host[k] = h
+                host[k] = _to_pinned(t, st)
         st.synchronize()
         n = {k: v.numpy() for k, v in host.items()}
         bin_id = n['bin_id'].astype(np.int64) if 'bin_id' in n else None
@@ -191,22 +206,9 @@ class DeviceRendered:
             with torch.cuda.stream(st):
                 for ok, bk in byte_cols:
                     b0, b1 = int(n[ok][r0]), int(n[ok][r1])
-                    t = cols[bk]
-                    h = torch.empty(max(b1 - b0, 1), dtype=t.dtype, pin_memory=True)[:b1 - b0]
-                    if b1 > b0:
-                        h.copy_(t[b0:b1], non_blocking=True)
-                    chunk[bk] = _Shifted(h.numpy(), b0)
+                    chunk[bk] = _Shifted(_to_pinned(cols[bk], st, b0, b1).numpy(), b0)
             st.synchronize()
-            rd = Rendered(n['a_off'], chunk['a_bytes'], n['b_off'], chunk['b_bytes'],
-                          n['is_rn'].view(bool), n['num_tokens'].view(np.uint16))
-            if self.masking:
-                rd.l_off, rd.l_bytes = n['l_off'], chunk['l_bytes']
-                rd.npy_off, rd.npy_bytes = n['npy_off'], chunk['npy_bytes']
-            if bin_id is not None:
-                rd.bin_id = bin_id
-            yield p0, p1, rd
-        for _, bk in byte_cols:
-            cols[bk].record_stream(st)
+            yield p0, p1, _rendered(n, chunk, n['is_rn'].view(bool), self.masking, bin_id)
         self.cols = None
 
 

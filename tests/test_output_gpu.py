@@ -107,6 +107,28 @@ def test_render_matches_python(ctx):
             assert rd.row(r) == exp[r]
 
 
+def _spy_host_copies(monkeypatch):
+    """Count DeviceRendered's host copies: {'to_host': [None per call], 'to_host_chunks':
+    [[ranges given, groups yielded] per call]}."""
+    from lddl_amd.output import DeviceRendered
+    calls = {'to_host': [], 'to_host_chunks': []}
+    real_host, real_chunks = DeviceRendered.to_host, DeviceRendered.to_host_chunks
+
+    def to_host(self, stream=None):
+        calls['to_host'].append(None)
+        return real_host(self, stream)
+
+    def to_host_chunks(self, part_rows, chunk_bytes, stream=None):
+        call = [len(part_rows) - 1, 0]
+        calls['to_host_chunks'].append(call)
+        for item in real_chunks(self, part_rows, chunk_bytes, stream):
+            call[1] += 1
+            yield item
+    monkeypatch.setattr(DeviceRendered, 'to_host', to_host)
+    monkeypatch.setattr(DeviceRendered, 'to_host_chunks', to_host_chunks)
+    return calls
+
+
 def _write_source(root, n_docs=300, seed=11):
     from lddl_amd import synth
     corp = synth.generate(seed=seed, n_bytes=n_docs * 3000, nonascii_frac=0.02)
@@ -131,8 +153,10 @@ def test_pretrain_cli_vs_oracle(tmp_path, monkeypatch, binned, params, workers, 
     partition per group; 0: the whole batch at once; None: the default 128 MiB)."""
     from lddl_amd import synth
     from lddl_amd.dask.bert import pretrain as P
+    from lddl_amd.dask.bert import writers as W
     if chunk is not None:
-        monkeypatch.setattr(P, '_D2H_CHUNK_BYTES', chunk)
+        monkeypatch.setattr(W, '_D2H_CHUNK_BYTES', chunk)
+    calls = _spy_host_copies(monkeypatch)
     from oracle import oracle as O
     src = tmp_path / 'source'
     _write_source(str(src))
@@ -153,6 +177,13 @@ def test_pretrain_cli_vs_oracle(tmp_path, monkeypatch, binned, params, workers, 
             prm = json.load(f)
     args = P.attach_args().parse_args(argv)
     P.main(args)
+    # which copy path the batches took: the patched chunk size is the one the writers read
+    if chunk == 0:
+        assert calls['to_host'] and not calls['to_host_chunks']
+    else:
+        assert calls['to_host_chunks'] and not calls['to_host']
+        if chunk == 1:  # one partition per group
+            assert all(groups == n_part for n_part, groups in calls['to_host_chunks'])
     # CPU replay: the same host partitions, the oracle tokenizer + pair/mask replay
     args = P.attach_args().parse_args(argv)
     parts = P.get_partitions(args)
@@ -308,17 +339,20 @@ def test_pretrain_cli_num_shards_balanced(tmp_path, monkeypatch, binned, masking
     get_bert_pretrain_data_loader consumes them. chunk = 1: the rendered rows leave the GPU one
     (shard, bin) range at a time."""
     from lddl_amd.balance import batch_shard_counts
-    from lddl_amd.dask.bert import pretrain as P0
+    from lddl_amd.dask.bert import writers as P0
     seen = []  # whether each sharded batch's ranges tiled its rows (the chunked copy ran)
+    nonempty = []  # the non-empty (shard, bin) ranges of each sharded batch
     real_order = P0._row_order
 
     def row_order(ranges):
         out = real_order(ranges)
         seen.append(out[2])
+        nonempty.append(sum(1 for _, _, r0, r1 in ranges if r1 > r0))
         return out
     monkeypatch.setattr(P0, '_row_order', row_order)
     if chunk is not None:
         monkeypatch.setattr(P0, '_D2H_CHUNK_BYTES', chunk)
+    calls = _spy_host_copies(monkeypatch)
 
     def dealt(batches, S):  # batches: bin b's rows per GPU batch -> rows per shard
         out, prior = [[] for _ in range(S)], 0
@@ -344,6 +378,8 @@ def test_pretrain_cli_num_shards_balanced(tmp_path, monkeypatch, binned, masking
         ['--sink', 'x', '--gpu-batch-bytes', '1', '--shuffle-group-bytes', '1']),
         P.plan_partitions(args))) == n_part  # one batch per partition in shards_b
     assert seen and all(seen)  # every batch took the chunked copy
+    if chunk == 1:  # one (shard, bin) range per group: at least one batch's non-empty ranges
+        assert sum(groups for _, groups in calls['to_host_chunks']) >= max(nonempty)
     ns = json.loads((tmp_path / 'shards' / '.num_samples.json').read_text())
     ns_b = json.loads((tmp_path / 'shards_b' / '.num_samples.json').read_text())
     assert ns == ns_b  # the same counts per shard (N / N+1 after every batch)

@@ -57,7 +57,7 @@ def test_sharded_row_order_with_empty_ranges():
     shards that got no rows of a bin have empty ranges that start where the next bin's first
     non-empty range starts. Sorted by (r0, r1) they still tile the rows, so the chunked copy runs
     (sorting on r0 alone put the empty range after the non-empty one)."""
-    from lddl_amd.dask.bert.pretrain import _row_order
+    from lddl_amd.dask.bert.writers import _row_order
     rng = np.random.default_rng(5)
     for trial in range(200):
         S, B = int(rng.integers(1, 9)), int(rng.integers(1, 6))
