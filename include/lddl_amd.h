@@ -519,6 +519,48 @@ int lddl_collate_seqpack_masked(lddl_ctx* ctx, void* stream, const uint8_t* d_by
                                 int64_t ignore_index, int64_t vocab_len, uint64_t seed,
                                 uint64_t counter, int32_t whole_word);
 
+/* ---------------------------------------------------------------------------------------------
+ * Collate from a pair table (past the reference: the online loader, lddl_amd/torch/online.py).
+ * The input is a lddl_pairs_emit table, ids of lddl_ctx_id_bytes() bytes: pair q has A =
+ * d_tokens[tok_off[q], tok_off[q] + len_a[q]), B = the rest up to tok_off[q+1], and with static
+ * masking the positions d_pos[pos_off[q], pos_off[q+1]) ([CLS] A [SEP] B [SEP] coordinates) with
+ * the original ids d_lab at the same indices. Output row i is pair d_rows[i] (d_rows NULL = the
+ * identity); outputs int64 [batch, seq_len], d_next_sentence_labels int64 [batch] = is_rn.
+ *
+ * The outputs are bit-identical to what the string entry points write for the strings
+ * lddl_render_write makes of the same pairs in the same order, with equal seq_len, seed and
+ * counter (the Philox index of slot x of row i is i * seq_len + x), for every vocab in which no
+ * two lines hold the same string:
+ *   lddl_collate_pairs         lddl_collate_encode. Static masking (d_pos, d_lab, d_pos_off given:
+ *                              writes d_labels, unmasked slots = ignore_index; a position >=
+ *                              seq_len is dropped, the host refuses it with IndexError) or none
+ *                              (all three NULL: writes d_special_tokens_mask). The output that is
+ *                              not written may be NULL.
+ *   lddl_collate_pairs_masked  lddl_collate_encode_masked, or with whole_word != 0
+ *                              lddl_collate_encode_masked_ww.
+ * A pair longer than seq_len is refused on the host (ValueError); on the device its slots past
+ * the row are not written. One wave per row, 64-bit offsets, every output element written once.
+ * batch <= 0 returns 0. Both fail with -1 before anything is launched on a NULL context, a NULL
+ * table array or required output, static inputs given in part, or a vocab without [CLS] and
+ * [SEP] (masked: and [MASK]).
+ * ------------------------------------------------------------------------------------------- */
+int lddl_collate_pairs(lddl_ctx* ctx, void* stream, const void* d_tokens, const int64_t* d_tok_off,
+                       const int32_t* d_len_a, const uint8_t* d_is_rn, const uint16_t* d_pos,
+                       const void* d_lab, const int64_t* d_pos_off, const int64_t* d_rows,
+                       int32_t batch, int32_t seq_len, int64_t* d_input_ids,
+                       int64_t* d_token_type_ids, int64_t* d_attention_mask,
+                       int64_t* d_special_tokens_mask, int64_t* d_labels,
+                       int64_t* d_next_sentence_labels, int64_t ignore_index);
+
+int lddl_collate_pairs_masked(lddl_ctx* ctx, void* stream, const void* d_tokens,
+                              const int64_t* d_tok_off, const int32_t* d_len_a,
+                              const uint8_t* d_is_rn, const int64_t* d_rows, int32_t batch,
+                              int32_t seq_len, int64_t* d_input_ids, int64_t* d_token_type_ids,
+                              int64_t* d_attention_mask, int64_t* d_labels,
+                              int64_t* d_next_sentence_labels, float mlm_probability,
+                              int64_t ignore_index, int64_t vocab_len, uint64_t seed,
+                              uint64_t counter, int32_t whole_word);
+
 #ifdef __cplusplus
 }
 #endif

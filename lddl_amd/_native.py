@@ -103,6 +103,13 @@ SIGNATURES = {
                                                    c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp,
                                                    c_vp, c_vp, c_vp, ctypes.c_float, c_i64, c_i64,
                                                    c_u64, c_u64, c_i32]),
+    'lddl_collate_pairs': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_i64]),
+    'lddl_collate_pairs_masked': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                                 c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                 ctypes.c_float, c_i64, c_i64, c_u64, c_u64,
+                                                 c_i32]),
 }
 
 

@@ -1,0 +1,518 @@
+"""Online BERT pretraining loader (past the reference): corpus text -> [B, L] batches
+on the device, with no parquet shards, no DataLoader workers and no fork in between.
+
+    text blocks --corpus.iter_doc_batches (host threads)--> one *round* of partitions
+      --gpu_batch.make_batch_pairs (Punkt, WordPiece, NSP pairs, static masking)--> PairBatch
+      + the carry of the round before --output.bin_stable--> rows per bin --seeded shuffle-->
+      batches of batch_size rows --collate_pairs (lddl_collate_pairs[_masked])--> dict of tensors
+
+`collate_pairs` reads the pair table directly: the ids never become strings. The pure host
+pieces (`cut_round`, `step_order`, `count_rounds`, `validate_args`) import nothing of the native
+library and run without a GPU.
+"""
+import os
+from types import SimpleNamespace
+
+import numpy as np
+
+from ..random import choices, seeded_state
+
+_M64 = (1 << 64) - 1
+
+
+# ---- pure host helpers -----------------------------------------------------------------------
+def mix_seed(*parts):
+    """One non-negative 64-bit seed of a tuple of ints (order matters)."""
+    s = 0x9E3779B97F4A7C15
+    for p in parts:
+        s = ((s ^ (int(p) & _M64)) * 0x100000001B3 + 0x632BE59BD9B4E019) & _M64
+        s ^= s >> 29
+    return s
+
+
+def cut_round(new_rows, carry, batch_size, agreed=None, flush=False):
+    """The cut of one round: per bin, `new_rows` rows of the round's pairs plus `carry` rows left
+    by the round before -> (batches per bin, the new carry per bin).
+
+    Each bin yields total // batch_size full batches, or `agreed[b]` if that is fewer (the
+    all-reduce MIN over the ranks); what is not yielded is carried, so total == batches *
+    batch_size + new carry in every bin. flush=True (the end of an epoch, one rank, drop_last
+    off) also yields the remainder as one short batch per non-empty bin and leaves no carry."""
+    new_rows = np.asarray(new_rows, np.int64)
+    carry = np.asarray(carry, np.int64)
+    if batch_size < 1:
+        raise ValueError('batch_size must be >= 1')
+    if new_rows.shape != carry.shape or (new_rows < 0).any() or (carry < 0).any():
+        raise ValueError('rows per bin and carry per bin must be non-negative and of one shape')
+    total = new_rows + carry
+    batches = total // batch_size
+    if agreed is not None:
+        batches = np.minimum(batches, np.asarray(agreed, np.int64))
+    left = total - batches * batch_size
+    if flush:
+        return batches + (left > 0), np.zeros_like(left)
+    return batches, left
+
+
+def step_order(seed, sizes):
+    """The bin of every step of a round, as `Binned` draws it: sizes[b] = the sizes (rows) of bin
+    b's batches in the order they are yielded; each step picks a bin with
+    random.Random(seed).choices(bins, weights=rows remaining). A function of (seed, sizes)
+    alone, so ranks that agree on the sizes agree on the order."""
+    remaining = [int(sum(s)) for s in sizes]
+    nxt = [0] * len(sizes)
+    state = seeded_state(seed)
+    order = []
+    bins = list(range(len(sizes)))
+    for _ in range(sum(len(s) for s in sizes)):
+        c, state = choices(bins, weights=remaining, k=1, rng_state=state)
+        b = c[0]
+        assert nxt[b] < len(sizes[b])
+        remaining[b] -= int(sizes[b][nxt[b]])
+        nxt[b] += 1
+        order.append(b)
+    assert sum(remaining) == 0
+    return order
+
+
+def count_rounds(ns, blocks, rank, world):
+    """GPU batches (rounds) `corpus.iter_doc_batches` yields for `rank`: known from the block
+    list alone, so every rank knows every rank's count."""
+    from ..dask.bert.corpus import greedy, rank_batches
+    n = 0
+    for batch in rank_batches(ns, blocks, rank, world):
+        parts = [p for g in batch for p in g]
+        n += len(greedy(parts, lambda p: blocks[p].nbytes, ns.gpu_batch_bytes))
+    return n
+
+
+def validate_args(wikipedia=None, books=None, common_crawl=None, vocab_file=None, batch_size=None,
+                  target_seq_length=128, bin_size=None, duplicate_factor=1, static_masking=False,
+                  masked_lm_ratio=0.15, mlm_probability=0.15, whole_word_masking=False,
+                  rng='native', block_size=None, num_blocks=None, sample_ratio=1.0,
+                  sequence_length_alignment=8, rank=None, world=None, **_):
+    """Every argument error of get_bert_pretrain_online_data_loader, raised before the GPU (or
+    the corpus) is touched."""
+    if wikipedia is None and books is None and common_crawl is None:
+        raise ValueError('no corpus given: pass wikipedia=, books= or common_crawl= (the '
+                         "'source' directory of each)")
+    for name, p in (('wikipedia', wikipedia), ('books', books), ('common_crawl', common_crawl)):
+        if p is not None and not os.path.isdir(p):
+            raise FileNotFoundError('{}={!r} is not a directory'.format(name, p))
+    if not isinstance(vocab_file, str) or not os.path.isfile(vocab_file):
+        raise FileNotFoundError('vocab_file {!r}: a local vocab.txt is required (offline)'.format(
+            vocab_file))
+    if not isinstance(batch_size, int) or isinstance(batch_size, bool) or batch_size < 1:
+        raise ValueError('batch_size must be a positive int')
+    if not isinstance(target_seq_length, int) or target_seq_length < 3:
+        raise ValueError('target_seq_length must be an int >= 3')
+    if bin_size is not None:  # the CLI's rule (preprocess_bert_pretrain)
+        if not isinstance(bin_size, int) or bin_size < 1:
+            raise ValueError('bin_size must be a positive int')
+        if bin_size > target_seq_length:
+            raise ValueError('Please provide a bin size that is <= target-seq-length')
+        if target_seq_length % bin_size != 0:
+            raise ValueError('Please provide a bin size that can divide the target sequence '
+                             'length.')
+    if block_size is not None and num_blocks is not None:
+        raise ValueError('Only one of num_blocks or blocksize needs to be set!')
+    if rng not in ('native', 'replay'):
+        raise ValueError("rng must be 'native' or 'replay'")
+    if whole_word_masking and static_masking and rng != 'native':
+        raise ValueError("whole_word_masking=True with static_masking=True needs rng='native' "
+                         '(the replay mode reproduces the reference, which has no whole-word '
+                         'masking)')
+    if duplicate_factor < 1:
+        raise ValueError('duplicate_factor must be >= 1')
+    if not 0 < sample_ratio <= 1:
+        raise ValueError('sample_ratio must be in (0, 1]')
+    if not 0 <= mlm_probability <= 1 or not 0 <= masked_lm_ratio <= 1:
+        raise ValueError('mlm_probability and masked_lm_ratio must be in [0, 1]')
+    if sequence_length_alignment < 1:
+        raise ValueError('sequence_length_alignment must be >= 1')
+    if (rank is None) != (world is None):
+        raise ValueError('pass both rank and world, or neither')
+    if rank is not None and not 0 <= rank < world:
+        raise ValueError('rank must be in [0, world)')
+
+
+# ---- the collate -----------------------------------------------------------------------------
+def _roundup(n, a):
+    return ((int(n) - 1) // a + 1) * a
+
+
+def collate_pairs(ctx, pb, rows=None, sequence_length_alignment=8, ignore_index=-1, mask=None,
+                  whole_word=False, seq_len=None, *, check=True):
+    """`encode_packed` for rows `rows` (int64 cuda tensor of pair indices, None = all, in order)
+    of the PairBatch `pb`, read from the pair table itself (lddl_collate_pairs /
+    lddl_collate_pairs_masked): the dict encode_packed returns for the same samples rendered to
+    strings, bit for bit: input_ids, token_type_ids, attention_mask, next_sentence_labels and
+    `labels` (a table with static masking, or mask=(mlm_probability, seed, counter), with
+    whole_word as in encode_packed) or `special_tokens_mask`.
+
+    seq_len=None computes L = roundup(longest row, sequence_length_alignment) from the rows,
+    which costs one device sync. check=True (also one sync) refuses on the host what the string
+    path refuses: a row index outside the table (IndexError), a pair longer than seq_len
+    (ValueError), a static position >= seq_len (IndexError). The online loader, whose rows and
+    widths come from the table itself, passes seq_len and check=False and never waits."""
+    import torch
+    from .._native import check as _check, lib
+    from ..context import _ptr, _stream
+    dev = ctx.device
+    static = pb.pos is not None
+    if pb.tokens.element_size() != ctx.id_bytes or (
+            static and pb.labels.element_size() != ctx.id_bytes):
+        raise ValueError('pair table ids are {}-byte, the context collates {}-byte ids'.format(
+            pb.tokens.element_size(), ctx.id_bytes))
+    n = pb.n_pairs
+    if rows is not None:
+        assert rows.dtype == torch.int64 and rows.is_cuda and rows.is_contiguous()
+    B = n if rows is None else rows.numel()
+    if B and (seq_len is None or check):
+        ntok = pb.num_tokens
+        if rows is None:
+            stat = [ntok.new_zeros(()), ntok.new_full((), n - 1), ntok.max()]
+        else:
+            stat = [rows.min(), rows.max(), ntok[rows.clamp(0, n - 1)].max()]
+        if static and pb.pos.numel():
+            sel = torch.ones(n, dtype=torch.bool, device=dev)
+            if rows is not None:
+                sel = torch.zeros(n, dtype=torch.bool, device=dev)
+                sel[rows.clamp(0, n - 1)] = True
+            seg = torch.repeat_interleave(torch.arange(n, device=dev),
+                                          pb.pos_off[1:] - pb.pos_off[:-1],
+                                          output_size=pb.pos.numel())
+            p = pb.pos.to(torch.int64) & 0xFFFF  # uint16 positions in int16 storage
+            stat.append(torch.where(sel[seg], p, torch.zeros_like(p)).max())
+        stat = torch.stack(stat).tolist()  # the one sync
+        if stat[0] < 0 or stat[1] >= n:
+            raise IndexError('rows hold {}..{}, the table has {} pairs'.format(stat[0], stat[1], n))
+        if seq_len is None:
+            seq_len = _roundup(stat[2], sequence_length_alignment)
+        if stat[2] > seq_len:
+            raise ValueError('a pair of {} tokens does not fit the sequence length {}'.format(
+                stat[2], seq_len))
+        if len(stat) > 3 and stat[3] >= seq_len:  # the reference's labels[i][positions] raises
+            raise IndexError('masked_lm_positions holds {} >= sequence length {}'.format(
+                stat[3], seq_len))
+    L = int(seq_len or 0)
+    out = {k: torch.empty(B, L, dtype=torch.long, device=dev)
+           for k in ('input_ids', 'token_type_ids', 'attention_mask')}
+    nsl = out['next_sentence_labels'] = torch.empty(B, dtype=torch.long, device=dev)
+    head = (ctx.handle, _stream(), _ptr(pb.tokens), _ptr(pb.tok_off), _ptr(pb.len_a),
+            _ptr(pb.is_random_next))
+    outs = (_ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']))
+    if mask is not None and not static:
+        p, seed, counter = mask
+        labels = out['labels'] = torch.empty(B, L, dtype=torch.long, device=dev)
+        _check(lib.lddl_collate_pairs_masked(*head, _ptr(rows), B, L, *outs, _ptr(labels),
+                                             _ptr(nsl), float(p), ignore_index, len(ctx),
+                                             int(seed) & _M64, int(counter) & _M64,
+                                             1 if whole_word else 0))
+        return out
+    key = 'labels' if static else 'special_tokens_mask'
+    t = out[key] = torch.empty(B, L, dtype=torch.long, device=dev)
+    st = (_ptr(pb.pos), _ptr(pb.labels), _ptr(pb.pos_off)) if static else (None, None, None)
+    _check(lib.lddl_collate_pairs(*head, *st, _ptr(rows), B, L, *outs,
+                                  None if static else _ptr(t), _ptr(t) if static else None,
+                                  _ptr(nsl), ignore_index))
+    return out
+
+
+# ---- the loader ------------------------------------------------------------------------------
+def _concat_tables(pb, carry):
+    """[pb | carry] as one PairBatch (device copies; offsets rebased without a sync)."""
+    import torch
+    from ..pairs import PairBatch
+    if carry is None or carry.n_pairs == 0:
+        return pb
+    if pb is None or pb.n_pairs == 0:
+        return carry
+    out = PairBatch(torch.cat([pb.tokens, carry.tokens]),
+                    torch.cat([pb.tok_off, carry.tok_off[1:] + pb.tok_off[-1]]),
+                    torch.cat([pb.len_a, carry.len_a]),
+                    torch.cat([pb.is_random_next, carry.is_random_next]))
+    if pb.pos is not None:
+        out.pos = torch.cat([pb.pos, carry.pos])
+        out.labels = torch.cat([pb.labels, carry.labels])
+        out.pos_off = torch.cat([pb.pos_off, carry.pos_off[1:] + pb.pos_off[-1]])
+    return out
+
+
+class _Round:
+    """One round, cut: the table, the row list (bin-major, every bin shuffled; yielded rows
+    first, then the carried ones) and per bin the [r0, r1) row ranges and widths of its
+    batches."""
+    __slots__ = ('table', 'rows', 'ranges', 'widths')
+
+
+class OnlineBertPretrainLoader:
+    """The iterable get_bert_pretrain_online_data_loader returns. Each iter() is one epoch.
+    After an epoch, `dropped_samples` is the number of pairs that were made but not yielded
+    (`dropped_per_bin` per bin), `num_rounds` the rounds every rank ran, and `stats` (if set to
+    a dict before iterating) receives per-round host timings."""
+
+    def __init__(self, **kw):
+        validate_args(**kw)
+        self._kw = kw
+        self._epoch = kw['start_epoch']
+        self._ctx = self._ctx_prod = None
+        self._side = None
+        self._logger = None
+        self.dropped_samples = 0
+        self.dropped_per_bin = None
+        self.num_rounds = None
+        self.stats = None
+        T = kw['target_seq_length']
+        self.bin_size = kw['bin_size'] if kw['bin_size'] is not None else T
+        self.nbins = T // self.bin_size
+
+    def __len__(self):
+        raise TypeError('the online loader has no length: the number of pairs is not known '
+                        'before the text is read and paired')
+
+    # -- setup (first iter(): the GPU is not touched before) --
+    def _setup(self):
+        import torch
+        from .. import punkt
+        from ..context import Context
+        from ..dask.bert.corpus import punkt_params
+        from .log import DatasetLogger
+        from .utils import get_rank, get_world_size
+        kw = self._kw
+        if kw['rank'] is None:
+            self.rank, self.world = get_rank(), get_world_size()
+        else:
+            self.rank, self.world = kw['rank'], kw['world']
+        lower = kw['tokenizer_kwargs'].get('do_lower_case', True)
+        pp = kw['punkt_params']
+        if pp is None or isinstance(pp, str):
+            pp = punkt_params(SimpleNamespace(punkt_params=pp))
+        # two contexts: the producer thread's (segment / tokenize / pairs hold per-call state)
+        # and the consumer's (binning, carry, collate)
+        self._ctx = Context(kw['vocab_file'], do_lower_case=lower)
+        self._ctx_prod = Context(kw['vocab_file'], do_lower_case=lower)
+        punkt.set_params(self._ctx_prod, pp)
+        self._side = torch.cuda.Stream(device=self._ctx.device)
+        # the cut of a round waits for the GPU twice (rows per bin, widths): on a stream of its
+        # own, so that those waits never drain what the caller has queued on its stream
+        self._cut_stream = torch.cuda.Stream(device=self._ctx.device)
+        self._logger = DatasetLogger()
+
+    def _namespace(self, epoch):
+        """The preprocessor's argument namespace of this epoch (seed = base_seed + epoch)."""
+        kw = self._kw
+        return SimpleNamespace(
+            wikipedia=kw['wikipedia'], books=kw['books'], common_crawl=kw['common_crawl'],
+            wikipedia_lang=kw['wikipedia_lang'], block_size=kw['block_size'],
+            num_blocks=kw['num_blocks'], sample_ratio=kw['sample_ratio'],
+            seed=kw['base_seed'] + epoch, target_seq_length=kw['target_seq_length'],
+            duplicate_factor=kw['duplicate_factor'], masking=bool(kw['static_masking']),
+            short_seq_prob=kw['short_seq_prob'], masked_lm_ratio=kw['masked_lm_ratio'],
+            rng=kw['rng'],
+            whole_word_masking=bool(kw['whole_word_masking'] and kw['static_masking']),
+            bin_size=kw['bin_size'], gpu_batch_bytes=kw['gpu_batch_bytes'],
+            shuffle_group_bytes=kw['shuffle_group_bytes'], read_threads=kw['read_threads'])
+
+    def __iter__(self):
+        if self._ctx is None:
+            self._setup()
+        epoch = self._epoch
+        self._epoch += 1
+        return self._run_epoch(epoch)
+
+    # -- the producer: runs in corpus.prefetch's thread, on the side stream --
+    def _produce(self, ns, text_batches):
+        import torch
+        from ..dask.bert.gpu_batch import make_batch_pairs
+        ctx = self._ctx_prod
+        with torch.cuda.device(ctx.device), torch.cuda.stream(self._side):
+            for partitions, corpus in text_batches:
+                pb = make_batch_pairs(ctx, ns, partitions, corpus)
+                ev = torch.cuda.Event()
+                ev.record(self._side)
+                yield pb, ev
+
+    @staticmethod
+    def _adopt(stream, ev, pb, *more):
+        """Order `stream` after the event of the stream that made the table `pb` (and the
+        tensors `more`) and let it use their memory."""
+        stream.wait_event(ev)
+        for t in (pb.tokens, pb.tok_off, pb.len_a, pb.is_random_next, pb.pos, pb.labels,
+                  pb.pos_off, pb.part_off) + more:
+            if t is not None:
+                t.record_stream(stream)
+
+    def _agree(self, local):
+        """all_reduce(MIN) of the batches per bin; on the device iff the backend is nccl."""
+        import torch
+        import torch.distributed as dist
+        if self.world == 1:
+            return local
+        dev = self._ctx.device if dist.get_backend() == 'nccl' else 'cpu'
+        t = torch.from_numpy(np.asarray(local, np.int64)).to(dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MIN)
+        return t.cpu().numpy()
+
+    def _cut(self, table, carry_n, epoch, rnd, flush):
+        """Bin, shuffle and cut `table` (new pairs and the carry, of which carry_n[b] rows are
+        bin b's): one host wait for the rows per bin, one for the widths of all batches; returns
+        (_Round, the new carry table, its rows per bin)."""
+        import torch
+        from ..balance import HipOps, _gather_table
+        from ..output import bin_stable
+        ctx, dev, bs = self._ctx, self._ctx.device, self._kw['batch_size']
+        nb = self.nbins
+        n = 0 if table is None else table.n_pairs
+        if n:
+            perm, _, cnt = bin_stable(ctx, tok_off=table.tok_off, bin_size=self.bin_size, nbins=nb,
+                                      with_bin_id=False)
+            total = cnt.cpu().numpy()  # host wait 1
+        else:
+            total = np.zeros(nb, np.int64)
+        new = total - carry_n  # a carried row falls into the bin it came from
+        local, _ = cut_round(new, carry_n, bs, flush=flush)
+        batches = local if flush else self._agree(local)
+        batches, left = cut_round(new, carry_n, bs, agreed=batches, flush=flush)
+        R = _Round()
+        R.table, R.rows, R.ranges, R.widths = table, None, [[] for _ in range(nb)], None
+        if not n:
+            return R, None, left
+        # rows: per bin a seeded permutation of the bin's segment of perm; the yielded rows of
+        # all bins first, then the carried rows (bin-major)
+        off = np.concatenate([[0], np.cumsum(total)])
+        idx_y, idx_c, r0 = [], [], 0
+        for b in range(nb):
+            k = int(total[b])
+            if not k:
+                continue
+            sh = off[b] + np.random.Generator(np.random.PCG64(mix_seed(
+                self._kw['base_seed'], epoch, self.rank, rnd, b))).permutation(k)
+            ny = k - int(left[b])
+            idx_y.append(sh[:ny])
+            idx_c.append(sh[ny:])
+            for j in range(int(batches[b])):
+                R.ranges[b].append((r0 + j * bs, r0 + min((j + 1) * bs, ny)))
+            r0 += ny
+        idx = np.concatenate(idx_y + idx_c).astype(np.int64)
+        rows = perm[torch.from_numpy(idx).to(dev)]
+        n_y = r0
+        R.rows = rows[:n_y]
+        carry = None
+        if n_y < n:  # the carry: a small table of its own (lddl_gather_ragged / lddl_take)
+            carry = _gather_table(HipOps(ctx), table, None, rows[n_y:].contiguous())
+        if n_y:
+            # widths of all batches of the round in one copy: row r of the list belongs to batch
+            # seg[r]; L = roundup(max num_tokens, alignment)
+            flat = [rg for b in range(nb) for rg in R.ranges[b]]
+            sizes = torch.tensor([b1 - b0 for b0, b1 in flat], device=dev)
+            seg = torch.repeat_interleave(torch.arange(len(flat), device=dev), sizes,
+                                          output_size=n_y)
+            ntok = table.num_tokens[R.rows]
+            mx = torch.zeros(len(flat), dtype=ntok.dtype, device=dev).scatter_reduce_(
+                0, seg, ntok, 'amax', include_self=True)
+            mx = mx.cpu().numpy()  # host wait 2
+            a = self._kw['sequence_length_alignment']
+            it = iter(((mx - 1) // a + 1) * a)
+            R.widths = [[int(next(it)) for _ in R.ranges[b]] for b in range(nb)]
+        return R, carry, left
+
+    def _run_epoch(self, epoch):
+        import time
+        import torch
+        from ..dask.bert.corpus import iter_doc_batches, plan_partitions, prefetch
+        from .bert import mask_seed
+        kw = self._kw
+        ns = self._namespace(epoch)
+        blocks = plan_partitions(ns)
+        n_rounds = max(count_rounds(ns, blocks, r, self.world) for r in range(self.world))
+        self.num_rounds = n_rounds
+        text = prefetch(iter_doc_batches(ns, self.rank, self.world, blocks))
+        produced = prefetch(self._produce(ns, text))
+        nb = self.nbins
+        static = bool(kw['static_masking'])
+        extra = kw['collate_fn'] or (lambda x: x)
+        keys = [mask_seed(kw['base_seed'], self.rank, b if kw['bin_size'] is not None else -1)
+                for b in range(nb)]
+        in_bin = [0] * nb  # index of the next batch of each bin this epoch
+        carry, carry_n = None, np.zeros(nb, np.int64)
+        flush_round = self.world == 1 and not kw['drop_last']
+        cut = self._cut_stream
+        for rnd in range(n_rounds + (1 if flush_round else 0)):
+            t0 = time.perf_counter()
+            flush = rnd == n_rounds
+            pb = item = None
+            if not flush:
+                item = next(produced, None)  # waits for the producer thread, not for the GPU
+            t1 = time.perf_counter()
+            with torch.cuda.stream(cut):  # (never across a yield: the caller's stream is its own)
+                if item is not None:
+                    pb = item[0]
+                    self._adopt(cut, item[1], pb)
+                table = _concat_tables(pb, carry)
+                if flush and (table is None or table.n_pairs == 0):
+                    break
+                R, carry, carry_n = self._cut(table, carry_n, epoch, rnd, flush)
+                ev = torch.cuda.Event()
+                ev.record(cut)
+            if R.rows is not None:  # the collates run on the caller's stream, after the cut
+                self._adopt(torch.cuda.current_stream(self._ctx.device), ev, R.table, R.rows)
+            del pb, table
+            if self.stats is not None:
+                self.stats.setdefault('round_wait_s', []).append(t1 - t0)
+                self.stats.setdefault('round_cut_s', []).append(time.perf_counter() - t1)
+            sizes = [[r1 - r0 for r0, r1 in R.ranges[b]] for b in range(nb)]
+            nxt = [0] * nb
+            for b in step_order(mix_seed(kw['base_seed'], epoch, rnd), sizes):
+                (r0, r1), L = R.ranges[b][nxt[b]], R.widths[b][nxt[b]]
+                nxt[b] += 1
+                mask = None
+                if not static:
+                    mask = (kw['mlm_probability'], keys[b], (epoch << 32) | in_bin[b])
+                in_bin[b] += 1
+                with torch.no_grad():
+                    enc = collate_pairs(self._ctx, R.table, R.rows[r0:r1],
+                                        kw['sequence_length_alignment'], kw['ignore_index'],
+                                        mask=mask, whole_word=kw['whole_word_masking'],
+                                        seq_len=L, check=False)
+                yield extra(enc)
+            del R
+        assert next(produced, None) is None
+        self.dropped_per_bin = carry_n
+        self.dropped_samples = int(carry_n.sum())
+        if self.dropped_samples:
+            msg = 'epoch {}: dropped {} samples short of a full batch (per bin: {})'.format(
+                epoch, self.dropped_samples, carry_n.tolist())
+            self._logger.to('rank').warning(msg)
+
+
+def get_bert_pretrain_online_data_loader(
+        wikipedia=None, books=None, common_crawl=None, wikipedia_lang='en', vocab_file=None,
+        batch_size=None, target_seq_length=128, bin_size=None, short_seq_prob=0.1,
+        duplicate_factor=1, static_masking=False, masked_lm_ratio=0.15, mlm_probability=0.15,
+        whole_word_masking=False, rng='native', block_size=None, num_blocks=None,
+        sample_ratio=1.0, base_seed=12345, start_epoch=0, rank=None, world=None,
+        gpu_batch_bytes=64 << 20, shuffle_group_bytes=1 << 30,
+        read_threads=min(os.cpu_count() or 1, 16), sequence_length_alignment=8, ignore_index=-1,
+        drop_last=True, tokenizer_kwargs={}, punkt_params=None, collate_fn=None):
+    """BERT pretraining batches straight from the corpus text (past the reference):
+    no preprocessing run, no shards, no DataLoader workers.
+
+    Returns an iterable; each iter() is one epoch and yields the dicts of
+    get_bert_pretrain_data_loader (input_ids, token_type_ids, attention_mask, labels,
+    next_sentence_labels; tensors on the current device). Epoch e's samples are exactly the pairs
+    `preprocess_bert_pretrain --seed (base_seed + e) --duplicate-factor D [--masking] --rng R`
+    writes for this rank's partitions (p % world == rank) with the same blocks, so every epoch
+    has fresh segment cuts, random-next partners and truncation. rank / world default to
+    torch.distributed's (else 0 / 1); a model-parallel job passes its data-parallel rank and
+    size.
+
+    static_masking=False masks in the collate (mlm_probability, whole_word_masking as in
+    get_bert_pretrain_data_loader); static_masking=True makes pairs with the preprocessor's
+    masking (masked_lm_ratio; rng='replay' is the reference's, bit for bit; whole-word needs
+    rng='native'), fresh each epoch. bin_size bins each round's pairs as --bin-size does; every
+    batch comes from one bin and all ranks draw the same bin at every step. With drop_last (or
+    more than one rank) the pairs short of a full batch at the end of the epoch are dropped and
+    counted in `dropped_samples`. There is no len(): TypeError."""
+    args = dict(locals())
+    return OnlineBertPretrainLoader(**args)
