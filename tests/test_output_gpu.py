@@ -1,7 +1,6 @@
 """Output stage on the GPU: per-partition binning (vs the reference's _to_dataframe_binned
 goldens and the oracle), string/npy rendering (vs Python ' '.join / np.save) and the
 `preprocess_bert_pretrain` CLI end to end (parquet files vs the oracle replay)."""
-import io
 import json
 import os
 
@@ -10,6 +9,7 @@ import pyarrow.parquet as pq
 import pytest
 
 from conftest import GOLDEN, VOCAB_UNCASED
+from render_util import py_rows as _py_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -63,26 +63,6 @@ def test_bin_many_partitions_vs_oracle(ctx):
             np.testing.assert_array_equal(perm[a:z] - a, eo)
             np.testing.assert_array_equal(bin_id[a:z], eb[eo])
             np.testing.assert_array_equal(counts[p], ec)
-
-
-def _py_rows(pairs, vocab, order=None):
-    """The reference's instance dicts (pretrain.py:345-358) from oracle/GPU pair arrays."""
-    rows = []
-    n = len(pairs['len_a'])
-    for q in (range(n) if order is None else order):
-        t = pairs['tokens'][pairs['tok_off'][q]:pairs['tok_off'][q + 1]]
-        na = pairs['len_a'][q]
-        d = {'A': ' '.join(vocab[i] for i in t[:na]), 'B': ' '.join(vocab[i] for i in t[na:]),
-             'is_random_next': bool(pairs['is_random_next'][q]),
-             'num_tokens': int(len(t) + 3)}
-        if 'pos' in pairs:
-            p0, p1 = pairs['pos_off'][q], pairs['pos_off'][q + 1]
-            buf = io.BytesIO()
-            np.save(buf, np.asarray(pairs['pos'][p0:p1], np.uint16))
-            d['masked_lm_positions'] = buf.getvalue()
-            d['masked_lm_labels'] = ' '.join(vocab[i] for i in pairs['labels'][p0:p1])
-        rows.append(d)
-    return rows
 
 
 def test_render_matches_python(ctx):
