@@ -561,6 +561,102 @@ int lddl_collate_pairs_masked(lddl_ctx* ctx, void* stream, const void* d_tokens,
                               int64_t ignore_index, int64_t vocab_len, uint64_t seed,
                               uint64_t counter, int32_t whole_word);
 
+/* ---------------------------------------------------------------------------------------------
+ * The row plan of sequence packing, made on the device (past the reference: the packed online
+ * loader). For every batch it computes exactly what lddl_amd/torch/seqpack.py's
+ * plan_rows(lengths, capacity) computes: first-fit decreasing, samples visited by length
+ * descending (ties: the lower index within the batch first), each into the lowest-numbered open
+ * row with room, else into a new row; samples sit back to back in a row in the order placed.
+ *
+ * Batch k is the samples d_rows[d_batch_off[k] .. d_batch_off[k+1]) (d_rows NULL = the
+ * identity); the batches tile [0, n_rows). The length of sample i is d_num_tokens[r], r =
+ * rows[i], or, with d_num_tokens NULL, d_tok_off[r+1] - d_tok_off[r] + 3 (lddl_bin_stable's
+ * convention). Every r must be a row of that array. Outputs, indexed like d_rows, every entry
+ * written:
+ *   d_dst[i]         row * capacity + start, relative to the batch's own [R, capacity] output
+ *   d_fill[i]        the sample's length; the last sample placed into a row also gets the row's
+ *                    unused tail
+ *   d_seq_in_row[i]  1-based index of the sample in its row
+ *   d_packed_idx[i]  position of the sample in (row, start) order = plan_rows' order^-1
+ *   d_num_rows[k]    R of batch k (an empty batch: 0)
+ * A sample longer than capacity takes no row: dst = -1, fill = 0, seq_in_row = 0, packed_idx =
+ * -1, and the rest of the batch is planned as if it were not there.
+ *
+ * One wave per batch, all batches in one launch, no host wait. A batch holds at most
+ * LDDL_SEQPLAN_MAX_BATCH samples. Fails with -1 before anything is launched on a NULL context,
+ * a NULL output or d_batch_off, both length sources NULL, capacity < 1, or n_rows >
+ * n_batches * LDDL_SEQPLAN_MAX_BATCH (some batch is then too large: with one batch this is the
+ * exact test). The offsets themselves are device memory, which the host does not wait for: a
+ * larger batch that this test cannot see is marked on the device (d_num_rows[k] = -1, its
+ * samples take no row), and a range outside [0, n_rows) writes only d_num_rows[k] = -1.
+ * n_batches <= 0 returns 0.
+ * ------------------------------------------------------------------------------------------- */
+#define LDDL_SEQPLAN_MAX_BATCH 1024
+int lddl_seqpack_plan(lddl_ctx* ctx, void* stream, const int32_t* d_num_tokens,
+                      const int64_t* d_tok_off, const int64_t* d_rows, int64_t n_rows,
+                      const int64_t* d_batch_off, int32_t n_batches, int32_t capacity,
+                      int64_t* d_dst, int32_t* d_fill, int32_t* d_seq_in_row,
+                      int32_t* d_packed_idx, int32_t* d_num_rows);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sequence-packed collate from a pair table (past the reference): to
+ * lddl_collate_seqpack[_masked] what lddl_collate_pairs[_masked] is to
+ * lddl_collate_encode[_masked]. The table and d_rows are lddl_collate_pairs'; d_dst, d_fill,
+ * d_seq_in_row and d_packed_idx are the plan of these `batch` samples (lddl_seqpack_plan's
+ * arrays from the batch's first sample on, or a host plan), out_rows its R.
+ *
+ * Outputs [out_rows, max_seq_length] int64: slot x < len of sample i's segment
+ * [dst[i], dst[i] + fill[i]) holds what lddl_collate_pairs[_masked] puts at [i, x], plus
+ * position_ids = x and sequence_ids = seq_in_row[i]; slots [len, fill) are padding with
+ * lddl_collate_seqpack's values. Per sample, at packed_idx[i]: d_next_sentence_labels (int64),
+ * d_cls_positions (int64, = dst[i]) and d_seq_lens (int32, = len). Every output element is
+ * written once by a plan whose segments tile the outputs. A sample whose segment does not lie
+ * inside the outputs, or with dst < 0, fill < len, len > max_seq_length, seq_in_row < 1 or
+ * packed_idx outside [0, batch), writes nothing.
+ *
+ *   lddl_collate_pairs_seqpack         static masking (d_pos, d_lab, d_pos_off: positions count
+ *                                      from the sample's [CLS], one >= len is dropped, the host
+ *                                      refuses it with IndexError; writes d_labels) or none (all
+ *                                      three NULL: writes d_special_tokens_mask)
+ *   lddl_collate_pairs_seqpack_masked  dynamic masking, per token or (whole_word != 0) whole
+ *                                      words in 64-slot windows from the sample's start. The
+ *                                      Philox index of slot x of sample i is i * draw_stride + x:
+ *                                      with draw_stride = the seq_len of lddl_collate_pairs_masked
+ *                                      and equal seed / counter the segment is bit-identical to
+ *                                      row i of its output.
+ * batch, out_rows or max_seq_length <= 0 returns 0. Both fail with -1 before anything is
+ * launched on a NULL context, a NULL table array, plan array or required output, static inputs
+ * given in part, a vocab without [CLS] and [SEP] (masked: and [MASK]), or (static masking)
+ * max_seq_length too long for the kernel's LDS staging.
+ * ------------------------------------------------------------------------------------------- */
+int lddl_collate_pairs_seqpack(lddl_ctx* ctx, void* stream, const void* d_tokens,
+                               const int64_t* d_tok_off, const int32_t* d_len_a,
+                               const uint8_t* d_is_rn, const uint16_t* d_pos, const void* d_lab,
+                               const int64_t* d_pos_off, const int64_t* d_rows, int32_t batch,
+                               const int64_t* d_dst, const int32_t* d_fill,
+                               const int32_t* d_seq_in_row, const int32_t* d_packed_idx,
+                               int32_t out_rows, int32_t max_seq_length, int64_t* d_input_ids,
+                               int64_t* d_token_type_ids, int64_t* d_attention_mask,
+                               int64_t* d_special_tokens_mask, int64_t* d_labels,
+                               int64_t* d_position_ids, int64_t* d_sequence_ids,
+                               int64_t* d_next_sentence_labels, int64_t* d_cls_positions,
+                               int32_t* d_seq_lens, int64_t ignore_index);
+
+int lddl_collate_pairs_seqpack_masked(lddl_ctx* ctx, void* stream, const void* d_tokens,
+                                      const int64_t* d_tok_off, const int32_t* d_len_a,
+                                      const uint8_t* d_is_rn, const int64_t* d_rows, int32_t batch,
+                                      const int64_t* d_dst, const int32_t* d_fill,
+                                      const int32_t* d_seq_in_row, const int32_t* d_packed_idx,
+                                      int32_t out_rows, int32_t max_seq_length,
+                                      int32_t draw_stride, int64_t* d_input_ids,
+                                      int64_t* d_token_type_ids, int64_t* d_attention_mask,
+                                      int64_t* d_labels, int64_t* d_position_ids,
+                                      int64_t* d_sequence_ids, int64_t* d_next_sentence_labels,
+                                      int64_t* d_cls_positions, int32_t* d_seq_lens,
+                                      float mlm_probability, int64_t ignore_index,
+                                      int64_t vocab_len, uint64_t seed, uint64_t counter,
+                                      int32_t whole_word);
+
 #ifdef __cplusplus
 }
 #endif

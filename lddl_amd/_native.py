@@ -110,6 +110,18 @@ SIGNATURES = {
                                                  c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                                  ctypes.c_float, c_i64, c_i64, c_u64, c_u64,
                                                  c_i32]),
+    'lddl_seqpack_plan': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'lddl_collate_pairs_seqpack': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                  c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                                  c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                  c_vp, c_vp, c_vp, c_i64]),
+    'lddl_collate_pairs_seqpack_masked': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                         c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                                         c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                                         c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                         ctypes.c_float, c_i64, c_i64, c_u64,
+                                                         c_u64, c_i32]),
 }
 
 

@@ -6,7 +6,10 @@ on the device, with no parquet shards, no DataLoader workers and no fork in betw
       + the carry of the round before --output.bin_stable--> rows per bin --seeded shuffle-->
       batches of batch_size rows --collate_pairs (lddl_collate_pairs[_masked])--> dict of tensors
 
-`collate_pairs` reads the pair table directly: the ids never become strings. The pure host
+`collate_pairs` reads the pair table directly: the ids never become strings. With sequence
+packing (get_bert_pretrain_online_packed_data_loader) the cut also plans the rows of
+every batch of the round on the device (plan_rows_device: lddl_seqpack_plan) and each step is
+collate_pairs_seqpacked (lddl_collate_pairs_seqpack[_masked]) instead. The pure host
 pieces (`cut_round`, `step_order`, `count_rounds`, `validate_args`) import nothing of the native
 library and run without a GPU.
 """
@@ -18,6 +21,7 @@ import numpy as np
 from ..random import choices, seeded_state
 
 _M64 = (1 << 64) - 1
+SEQPLAN_MAX_BATCH = 1024  # kSeqPlanMaxBatch (LDDL_SEQPLAN_MAX_BATCH, include/lddl_amd.h)
 
 
 # ---- pure host helpers -----------------------------------------------------------------------
@@ -90,9 +94,11 @@ def validate_args(wikipedia=None, books=None, common_crawl=None, vocab_file=None
                   target_seq_length=128, bin_size=None, duplicate_factor=1, static_masking=False,
                   masked_lm_ratio=0.15, mlm_probability=0.15, whole_word_masking=False,
                   rng='native', block_size=None, num_blocks=None, sample_ratio=1.0,
-                  sequence_length_alignment=8, rank=None, world=None, **_):
-    """Every argument error of get_bert_pretrain_online_data_loader, raised before the GPU (or
-    the corpus) is touched."""
+                  sequence_length_alignment=8, rank=None, world=None, max_seq_length=None,
+                  _packed=False, **_):
+    """Every argument error of get_bert_pretrain_online_data_loader (and, with _packed, of
+    get_bert_pretrain_online_packed_data_loader), raised before the GPU (or the corpus) is
+    touched."""
     if wikipedia is None and books is None and common_crawl is None:
         raise ValueError('no corpus given: pass wikipedia=, books= or common_crawl= (the '
                          "'source' directory of each)")
@@ -106,6 +112,15 @@ def validate_args(wikipedia=None, books=None, common_crawl=None, vocab_file=None
         raise ValueError('batch_size must be a positive int')
     if not isinstance(target_seq_length, int) or target_seq_length < 3:
         raise ValueError('target_seq_length must be an int >= 3')
+    if _packed:
+        # num_tokens <= target_seq_length, so every pair fits a row of max_seq_length slots
+        if not isinstance(max_seq_length, int) or isinstance(max_seq_length, bool) or \
+                max_seq_length < target_seq_length:
+            raise ValueError('max_seq_length must be an int >= target_seq_length ({}), not '
+                             '{!r}'.format(target_seq_length, max_seq_length))
+        if batch_size > SEQPLAN_MAX_BATCH:
+            raise ValueError('batch_size {} > {}: the device row planner holds at most that '
+                             'many samples per batch'.format(batch_size, SEQPLAN_MAX_BATCH))
     if bin_size is not None:  # the CLI's rule (preprocess_bert_pretrain)
         if not isinstance(bin_size, int) or bin_size < 1:
             raise ValueError('bin_size must be a positive int')
@@ -219,6 +234,179 @@ def collate_pairs(ctx, pb, rows=None, sequence_length_alignment=8, ignore_index=
     return out
 
 
+# ---- sequence packing: the plan and the collate ----------------------------------
+class DevicePlan:
+    """The row plans of a list of batches, on the device (plan_rows_device): dst, fill,
+    seq_in_row and packed_idx are indexed like the row list, num_rows[k] is batch k's R.
+    batch_off (host ints) and capacity are what the plan was made for."""
+    __slots__ = ('dst', 'fill', 'seq_in_row', 'packed_idx', 'num_rows', 'batch_off', 'capacity')
+
+    def tensors(self):
+        return (self.dst, self.fill, self.seq_in_row, self.packed_idx, self.num_rows)
+
+
+def plan_rows_device(ctx, pb_or_num_tokens, rows, batch_off, capacity, *, clamp=True,
+                     events=None):
+    """`seqpack.plan_rows` for every batch of a row list in one launch (lddl_seqpack_plan), with
+    no host wait: batch k is rows[batch_off[k]:batch_off[k + 1]] (rows: int64 cuda tensor of
+    table indices, None = the identity; batch_off: host ints that tile the list), a sample's
+    length comes from a PairBatch's tok_off (len(A) + len(B) + 3) or from an int32 cuda tensor
+    of num_tokens. Returns a DevicePlan; its arrays are bit for bit plan_rows' of each batch
+    (dst = row * capacity + start, packed_idx = the inverse of order).
+
+    A batch of more than SEQPLAN_MAX_BATCH samples raises ValueError before anything is
+    launched. clamp=True clamps `rows` into the table on the device, so that an index outside
+    it, which collate_pairs_seqpacked(check=True) then refuses, makes the planner read nothing
+    outside; a caller whose rows come from the table itself passes clamp=False. events: two
+    torch.cuda.Event recorded around the launch (measurements)."""
+    import torch
+    from .._native import check as _check, lib
+    from ..context import _ptr, _stream
+    dev = ctx.device
+    if isinstance(pb_or_num_tokens, torch.Tensor):
+        ntok, tok_off = pb_or_num_tokens, None
+        assert ntok.dtype == torch.int32 and ntok.is_cuda and ntok.is_contiguous()
+        n = ntok.numel()
+    else:
+        ntok, tok_off = None, pb_or_num_tokens.tok_off
+        n = pb_or_num_tokens.n_pairs
+    if rows is not None:
+        assert rows.dtype == torch.int64 and rows.is_cuda and rows.is_contiguous()
+    n_rows = n if rows is None else rows.numel()
+    off = np.asarray(batch_off, np.int64).reshape(-1)
+    nb = max(len(off) - 1, 0)
+    capacity = int(capacity)
+    if capacity < 1:
+        raise ValueError('capacity must be >= 1')
+    if nb and (off[0] != 0 or off[-1] != n_rows or (np.diff(off) < 0).any()):
+        raise ValueError('batch_off must rise from 0 to the number of rows ({})'.format(n_rows))
+    if nb and int(np.diff(off).max()) > SEQPLAN_MAX_BATCH:
+        raise ValueError('a batch of {} samples: the device row planner holds at most {}'.format(
+            int(np.diff(off).max()), SEQPLAN_MAX_BATCH))
+    plan = DevicePlan()
+    plan.batch_off, plan.capacity = off.tolist(), capacity
+    plan.dst = torch.empty(n_rows, dtype=torch.int64, device=dev)
+    plan.fill, plan.seq_in_row, plan.packed_idx = (
+        torch.empty(n_rows, dtype=torch.int32, device=dev) for _ in range(3))
+    plan.num_rows = torch.empty(nb, dtype=torch.int32, device=dev)
+    if not n_rows:
+        plan.num_rows.zero_()  # empty batches only
+    elif nb:
+        if clamp and rows is not None and n:
+            rows = rows.clamp(0, n - 1)
+        d_off = torch.from_numpy(off).to(dev)
+        if events is not None:
+            events[0].record()
+        _check(lib.lddl_seqpack_plan(ctx.handle, _stream(), _ptr(ntok), _ptr(tok_off), _ptr(rows),
+                                     n_rows, _ptr(d_off), nb, capacity, _ptr(plan.dst),
+                                     _ptr(plan.fill), _ptr(plan.seq_in_row),
+                                     _ptr(plan.packed_idx), _ptr(plan.num_rows)))
+        if events is not None:
+            events[1].record()
+    return plan
+
+
+def collate_pairs_seqpacked(ctx, pb, rows, plan, k, R, max_seq_length, draw_stride,
+                            ignore_index=-1, mask=None, whole_word=False, *, check=True):
+    """`encode_seqpacked` for batch `k` of the DevicePlan `plan` (plan_rows_device over the same
+    `pb` and `rows`), read from the pair table itself (lddl_collate_pairs_seqpack /
+    lddl_collate_pairs_seqpack_masked). Returns encode_seqpacked's dict: [R, max_seq_length]
+    input_ids, token_type_ids, attention_mask, position_ids, sequence_ids and labels (static
+    masking or mask=(mlm_probability, seed, counter); else special_tokens_mask), and per sample
+    in packed order next_sentence_labels, cls_positions and seq_lens (int32).
+
+    R is the batch's row count (plan.num_rows[k], which the online loader brings to the host
+    with the round's widths); None reads it here, which waits for the device. draw_stride is
+    the seq_len of the unpacked batch: with it and equal (seed, counter) sample i's segment is
+    bit for bit row i of collate_pairs(ctx, pb, rows[batch k], seq_len=draw_stride, ...).
+
+    check=True costs one sync and raises what the string path raises: IndexError for a row
+    outside the table, ValueError for a pair longer than max_seq_length, IndexError for a
+    static position >= its own sample's length (in a packed row it would land in the next
+    sample). The online loader passes check=False and never waits."""
+    import ctypes
+    import torch
+    from .._native import check as _check, lib
+    from ..context import _ptr, _stream
+    dev = ctx.device
+    static = pb.pos is not None
+    if pb.tokens.element_size() != ctx.id_bytes or (
+            static and pb.labels.element_size() != ctx.id_bytes):
+        raise ValueError('pair table ids are {}-byte, the context collates {}-byte ids'.format(
+            pb.tokens.element_size(), ctx.id_bytes))
+    L = int(max_seq_length)
+    if plan.capacity != L:
+        raise ValueError('the batch was planned for rows of {} slots, not {}'.format(
+            plan.capacity, L))
+    n = pb.n_pairs
+    b0, b1 = plan.batch_off[k], plan.batch_off[k + 1]
+    B = b1 - b0
+    if rows is not None:
+        assert rows.dtype == torch.int64 and rows.is_cuda and rows.is_contiguous()
+        rows = rows[b0:b1]
+    elif (b0, b1) != (0, n):
+        rows = torch.arange(b0, b1, device=dev)
+    if B and (check or R is None):
+        ntok = pb.num_tokens
+        if rows is None:
+            stat = [ntok.new_zeros(()), ntok.new_full((), n - 1), ntok.max()]
+        else:
+            stat = [rows.min(), rows.max(), ntok[rows.clamp(0, n - 1)].max()]
+        stat.append(plan.num_rows[k].to(ntok.dtype))
+        if static and pb.pos.numel():
+            sel = torch.ones(n, dtype=torch.bool, device=dev)
+            if rows is not None:
+                sel = torch.zeros(n, dtype=torch.bool, device=dev)
+                sel[rows.clamp(0, n - 1)] = True
+            seg = torch.repeat_interleave(torch.arange(n, device=dev),
+                                          pb.pos_off[1:] - pb.pos_off[:-1],
+                                          output_size=pb.pos.numel())
+            p = pb.pos.to(torch.int64) & 0xFFFF  # uint16 positions in int16 storage
+            over = torch.where(sel[seg], p - ntok[seg], torch.full_like(p, -1))
+            stat += [over.max(), p[over.argmax()]]
+        stat = torch.stack(stat).tolist()  # the one sync
+        if stat[0] < 0 or stat[1] >= n:
+            raise IndexError('rows hold {}..{}, the table has {} pairs'.format(stat[0], stat[1], n))
+        if stat[2] > L:
+            raise ValueError('a pair of {} tokens does not fit the sequence length {}'.format(
+                stat[2], L))
+        if len(stat) > 4 and stat[4] >= 0:
+            raise IndexError('masked_lm_positions holds {} >= the length {} of its '
+                             'sample'.format(stat[5], stat[5] - stat[4]))
+        if R is None:
+            R = stat[3]
+        elif R != stat[3]:
+            raise ValueError('R = {}, the plan of batch {} has {} rows'.format(R, k, stat[3]))
+    R = int(R or 0) if B else 0
+    names = ('input_ids', 'token_type_ids', 'attention_mask', 'position_ids', 'sequence_ids')
+    fused = mask is not None and not static
+    names += ('labels',) if fused or static else ('special_tokens_mask',)
+    out = {key: torch.empty(R, L, dtype=torch.long, device=dev) for key in names}
+    nsl = out['next_sentence_labels'] = torch.empty(B, dtype=torch.long, device=dev)
+    cls = out['cls_positions'] = torch.empty(B, dtype=torch.long, device=dev)
+    lens = out['seq_lens'] = torch.empty(B, dtype=torch.int32, device=dev)
+    head = (ctx.handle, _stream(), _ptr(pb.tokens), _ptr(pb.tok_off), _ptr(pb.len_a),
+            _ptr(pb.is_random_next))
+    at = lambda t: ctypes.c_void_p(t.data_ptr() + b0 * t.element_size())  # noqa: E731  &t[b0]
+    body = (_ptr(rows), B, at(plan.dst), at(plan.fill), at(plan.seq_in_row),
+            at(plan.packed_idx), R, L)
+    outs = (_ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']))
+    tail = (_ptr(out['position_ids']), _ptr(out['sequence_ids']), _ptr(nsl), _ptr(cls),
+            _ptr(lens))
+    if fused:
+        p, seed, counter = mask
+        _check(lib.lddl_collate_pairs_seqpack_masked(
+            *head, *body, int(draw_stride), *outs, _ptr(out['labels']), *tail, float(p),
+            ignore_index, len(ctx), int(seed) & _M64, int(counter) & _M64,
+            1 if whole_word else 0))
+        return out
+    st = (_ptr(pb.pos), _ptr(pb.labels), _ptr(pb.pos_off)) if static else (None, None, None)
+    _check(lib.lddl_collate_pairs_seqpack(
+        *head, *st, *body, *outs, _ptr(out.get('special_tokens_mask')), _ptr(out.get('labels')),
+        *tail, ignore_index))
+    return out
+
+
 # ---- the loader ------------------------------------------------------------------------------
 def _concat_tables(pb, carry):
     """[pb | carry] as one PairBatch (device copies; offsets rebased without a sync)."""
@@ -242,15 +430,17 @@ def _concat_tables(pb, carry):
 class _Round:
     """One round, cut: the table, the row list (bin-major, every bin shuffled; yielded rows
     first, then the carried ones) and per bin the [r0, r1) row ranges and widths of its
-    batches."""
-    __slots__ = ('table', 'rows', 'ranges', 'widths')
+    batches. The packed loader adds the round's DevicePlan, per bin the index of each batch in
+    it, and per bin the batches' packed row counts."""
+    __slots__ = ('table', 'rows', 'ranges', 'widths', 'plan', 'index', 'out_rows')
 
 
 class OnlineBertPretrainLoader:
     """The iterable get_bert_pretrain_online_data_loader returns. Each iter() is one epoch.
     After an epoch, `dropped_samples` is the number of pairs that were made but not yielded
     (`dropped_per_bin` per bin), `num_rounds` the rounds every rank ran, and `stats` (if set to
-    a dict before iterating) receives per-round host timings."""
+    a dict before iterating) receives per-round host timings (and, from the packed loader, a
+    pair of events around each round's row planner)."""
 
     def __init__(self, **kw):
         validate_args(**kw)
@@ -266,6 +456,7 @@ class OnlineBertPretrainLoader:
         T = kw['target_seq_length']
         self.bin_size = kw['bin_size'] if kw['bin_size'] is not None else T
         self.nbins = T // self.bin_size
+        self._packed = bool(kw.get('_packed'))
 
     def __len__(self):
         raise TypeError('the online loader has no length: the number of pairs is not known '
@@ -356,8 +547,9 @@ class OnlineBertPretrainLoader:
 
     def _cut(self, table, carry_n, epoch, rnd, flush):
         """Bin, shuffle and cut `table` (new pairs and the carry, of which carry_n[b] rows are
-        bin b's): one host wait for the rows per bin, one for the widths of all batches; returns
-        (_Round, the new carry table, its rows per bin)."""
+        bin b's): one host wait for the rows per bin, one for the widths of all batches (and,
+        packed, their row counts, in the same copy); returns (_Round, the new carry table, its
+        rows per bin)."""
         import torch
         from ..balance import HipOps, _gather_table
         from ..output import bin_stable
@@ -376,6 +568,7 @@ class OnlineBertPretrainLoader:
         batches, left = cut_round(new, carry_n, bs, agreed=batches, flush=flush)
         R = _Round()
         R.table, R.rows, R.ranges, R.widths = table, None, [[] for _ in range(nb)], None
+        R.plan = R.index = R.out_rows = None
         if not n:
             return R, None, left
         # rows: per bin a seeded permutation of the bin's segment of perm; the yielded rows of
@@ -411,10 +604,25 @@ class OnlineBertPretrainLoader:
             ntok = table.num_tokens[R.rows]
             mx = torch.zeros(len(flat), dtype=ntok.dtype, device=dev).scatter_reduce_(
                 0, seg, ntok, 'amax', include_self=True)
+            if self._packed:
+                # the row plans of all batches of the round in one launch; their row counts come
+                # to the host in the same copy as the widths
+                evs = None
+                if self.stats is not None:  # the planner's device time, read by the caller
+                    evs = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                    self.stats.setdefault('plan_events', []).append(evs)
+                R.plan = plan_rows_device(ctx, table, R.rows, [0] + [b1 for _, b1 in flat],
+                                          self._kw['max_seq_length'], clamp=False, events=evs)
+                mx = torch.cat([mx, R.plan.num_rows.to(mx.dtype)])
             mx = mx.cpu().numpy()  # host wait 2
             a = self._kw['sequence_length_alignment']
-            it = iter(((mx - 1) // a + 1) * a)
+            it = iter(((mx[:len(flat)] - 1) // a + 1) * a)
             R.widths = [[int(next(it)) for _ in R.ranges[b]] for b in range(nb)]
+            if self._packed:
+                it = iter(zip(range(len(flat)), mx[len(flat):]))
+                both = [[next(it) for _ in R.ranges[b]] for b in range(nb)]
+                R.index = [[k for k, _ in x] for x in both]
+                R.out_rows = [[int(r) for _, r in x] for x in both]
         return R, carry, left
 
     def _run_epoch(self, epoch):
@@ -456,7 +664,8 @@ class OnlineBertPretrainLoader:
                 ev = torch.cuda.Event()
                 ev.record(cut)
             if R.rows is not None:  # the collates run on the caller's stream, after the cut
-                self._adopt(torch.cuda.current_stream(self._ctx.device), ev, R.table, R.rows)
+                self._adopt(torch.cuda.current_stream(self._ctx.device), ev, R.table, R.rows,
+                            *(R.plan.tensors() if R.plan is not None else ()))
             del pb, table
             if self.stats is not None:
                 self.stats.setdefault('round_wait_s', []).append(t1 - t0)
@@ -464,17 +673,24 @@ class OnlineBertPretrainLoader:
             sizes = [[r1 - r0 for r0, r1 in R.ranges[b]] for b in range(nb)]
             nxt = [0] * nb
             for b in step_order(mix_seed(kw['base_seed'], epoch, rnd), sizes):
-                (r0, r1), L = R.ranges[b][nxt[b]], R.widths[b][nxt[b]]
+                j = nxt[b]
+                (r0, r1), L = R.ranges[b][j], R.widths[b][j]
                 nxt[b] += 1
                 mask = None
                 if not static:
                     mask = (kw['mlm_probability'], keys[b], (epoch << 32) | in_bin[b])
                 in_bin[b] += 1
                 with torch.no_grad():
-                    enc = collate_pairs(self._ctx, R.table, R.rows[r0:r1],
-                                        kw['sequence_length_alignment'], kw['ignore_index'],
-                                        mask=mask, whole_word=kw['whole_word_masking'],
-                                        seq_len=L, check=False)
+                    if self._packed:  # the same batch, planned in the cut: L is its draw stride
+                        enc = collate_pairs_seqpacked(
+                            self._ctx, R.table, R.rows, R.plan, R.index[b][j], R.out_rows[b][j],
+                            kw['max_seq_length'], L, kw['ignore_index'], mask=mask,
+                            whole_word=kw['whole_word_masking'], check=False)
+                    else:
+                        enc = collate_pairs(self._ctx, R.table, R.rows[r0:r1],
+                                            kw['sequence_length_alignment'], kw['ignore_index'],
+                                            mask=mask, whole_word=kw['whole_word_masking'],
+                                            seq_len=L, check=False)
                 yield extra(enc)
             del R
         assert next(produced, None) is None
@@ -516,3 +732,39 @@ def get_bert_pretrain_online_data_loader(
     counted in `dropped_samples`. There is no len(): TypeError."""
     args = dict(locals())
     return OnlineBertPretrainLoader(**args)
+
+
+def get_bert_pretrain_online_packed_data_loader(
+        max_seq_length=None, wikipedia=None, books=None, common_crawl=None, wikipedia_lang='en',
+        vocab_file=None, batch_size=None, target_seq_length=128, bin_size=None,
+        short_seq_prob=0.1, duplicate_factor=1, static_masking=False, masked_lm_ratio=0.15,
+        mlm_probability=0.15, whole_word_masking=False, rng='native', block_size=None,
+        num_blocks=None, sample_ratio=1.0, base_seed=12345, start_epoch=0, rank=None, world=None,
+        gpu_batch_bytes=64 << 20, shuffle_group_bytes=1 << 30,
+        read_threads=min(os.cpu_count() or 1, 16), sequence_length_alignment=8, ignore_index=-1,
+        drop_last=True, tokenizer_kwargs={}, punkt_params=None, collate_fn=None):
+    """get_bert_pretrain_online_data_loader with sequence packing (past the
+    reference): raw text in, packed rows out, no preprocessing run and no binning.
+
+    Every keyword is the online loader's. batch_size counts samples (at most SEQPLAN_MAX_BATCH);
+    each step's samples are packed first-fit decreasing into rows of max_seq_length slots
+    (an int >= target_seq_length, so every pair fits), planned (lddl_seqpack_plan) and collated
+    (lddl_collate_pairs_seqpack[_masked]) on the device. A batch is the dict of
+    get_bert_pretrain_packed_data_loader: [R, max_seq_length] input_ids, token_type_ids,
+    attention_mask, labels, position_ids and sequence_ids, and per sample in packed order
+    next_sentence_labels, cls_positions and seq_lens.
+
+    At step k it yields step k's batch of get_bert_pretrain_online_data_loader with the same
+    arguments, rearranged: the same samples, and the same masks slot for slot (the mask stream
+    is keyed by the sample's index in the batch and the unpacked batch's width). Seeds, the step
+    order, the carry across rounds, dropped_samples and the agreement between ranks are the
+    unpacked loader's.
+
+    bin_size stays allowed (batches then come from one bin, as with the parquet packed loader),
+    but packing replaces binning, and unbinned is the intended use: measured on the parquet
+    loader at seq 512, packing unbinned batches leaves 29 % fewer slots to the
+    training step, 99 % of them real, where 64 bins reach 92 %; and on this loader binning drops
+    up to a batch short of every bin at the end of an epoch (§18). There is no len():
+    TypeError."""
+    args = dict(locals())
+    return OnlineBertPretrainLoader(_packed=True, **args)
