@@ -657,6 +657,34 @@ int lddl_collate_pairs_seqpack_masked(lddl_ctx* ctx, void* stream, const void* d
                                       int64_t vocab_len, uint64_t seed, uint64_t counter,
                                       int32_t whole_word);
 
+/* ---------------------------------------------------------------------------------------------
+ * Compact MLM targets from dense labels (past the reference): the masked slots of
+ * d_labels int64[R * L] (label != ignore_index) in position order as fixed-shape arrays, for a
+ * gather in front of the MLM head. Asynchronous on `stream`; no context, no temporaries, no
+ * host wait, safe in a captured step. Every element of every output is written exactly once
+ * per call (the outputs need no initialisation).
+ *
+ * lddl_mlm_compact_rows: row r's masked slots x_0 < x_1 < ..., n_r of them, k = min(n_r, P):
+ *   d_positions[r * P + j] = x_j, d_ids[r * P + j] = labels[r, x_j], d_weights[r * P + j] = 1
+ *   for j < k; 0, ignore_index and 0 for k <= j < P; d_num_masked[r] = n_r, the true count, so
+ *   n_r > P tells an overflow (the first P slots in position order are the ones kept).
+ * lddl_mlm_compact_flat: the same over labels.view(-1): the flat indices r * L + x ascending in
+ *   d_flat_positions[capacity] with their labels in d_flat_ids[capacity]; the first
+ *   min(total, capacity) are kept, the rest is position 0 and id ignore_index;
+ *   d_num_masked[r] = n_r and *d_total (device int64) = sum of n_r.
+ *
+ * Both fail with -1 before anything is launched on a NULL pointer, R < 0, L < 0, L > 2^31 - 1
+ * (the counts are int32), or P < 1 / capacity < 1. R == 0 launches nothing for the rows form;
+ * the flat form then still writes its padding and *d_total = 0. L == 0 is R rows without a
+ * masked slot: all padding, counts 0.
+ * ------------------------------------------------------------------------------------------- */
+int lddl_mlm_compact_rows(void* stream, const int64_t* d_labels, int64_t R, int64_t L,
+                          int64_t ignore_index, int64_t P, int64_t* d_positions, int64_t* d_ids,
+                          float* d_weights, int32_t* d_num_masked);
+int lddl_mlm_compact_flat(void* stream, const int64_t* d_labels, int64_t R, int64_t L,
+                          int64_t ignore_index, int64_t capacity, int64_t* d_flat_positions,
+                          int64_t* d_flat_ids, int32_t* d_num_masked, int64_t* d_total);
+
 #ifdef __cplusplus
 }
 #endif

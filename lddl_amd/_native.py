@@ -122,6 +122,10 @@ SIGNATURES = {
                                                          c_vp, c_vp, c_vp, c_vp, c_vp,
                                                          ctypes.c_float, c_i64, c_i64, c_u64,
                                                          c_u64, c_i32]),
+    'lddl_mlm_compact_rows': (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                             c_vp, c_vp]),
+    'lddl_mlm_compact_flat': (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                             c_vp, c_vp]),
 }
 
 

@@ -3,7 +3,8 @@
 `get_bert_pretrain_data_loader`, `get_bert_pretrain_packed_data_loader` (sequence packing, past
 the reference) and the online loaders (`get_bert_pretrain_online_data_loader`, `collate_pairs`:
 raw text to batches without shards; `get_bert_pretrain_online_packed_data_loader`: the same with
-sequence packing planned and collated on the device; both past the reference) are resolved
+sequence packing planned and collated on the device; both past the reference) and the compact
+MLM targets (`compact_labels`, `CompactMLMTargets`: a `collate_fn` for every loader) are resolved
 lazily, so that DataLoader workers started with `spawn` / `forkserver` import only the
 worker-side modules (`packing`, `seqpack`, `datasets`), never the native library."""
 
@@ -17,4 +18,7 @@ def __getattr__(name):
                 'collate_pairs_seqpacked'):
         from . import online
         return getattr(online, name)
+    if name in ('compact_labels', 'CompactMLMTargets'):
+        from . import targets
+        return getattr(targets, name)
     raise AttributeError(name)
