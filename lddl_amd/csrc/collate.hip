@@ -25,7 +25,13 @@
 //                         it, and the word's masked / not masked decision is its head's draw. One
 //                         wave per row, heads found by ballot; kernels of their own, the plain
 //                         ones are untouched.
-#include "collate_dev.h"  // token_lookup, split_lookup, MaskDraw ..., ContBits, word_masked
+//
+// collate_dev.h holds what this unit shares with the other three collate units (the lookups, the
+// masking decision, the string-side arguments StrSample / StrLabels, SlotLayout for mask_special),
+// collate_host.h the host side of the entry points (the vocab check, the launch with its LDS
+// bound). encode_kernel owns its LDS staging, its two output loops and their predicates, written
+// out as in seqpack_kernel: collate_dev.h's comment at SlotLayout says why.
+#include "collate_host.h"  // need_vocab, mask_draw_of, launch_rows; collate_dev.h
 #include "common.h"
 #include "ctx.h"
 #include "device.h"
@@ -37,22 +43,13 @@ namespace lddl {
 namespace {
 
 struct EncodeArgs {
-  Tables T;
-  const uint8_t* bytes;
-  const int64_t* a_off;  // [B+1] A string of sample b = bytes[a_off[b], a_off[b+1])
-  const int64_t* b_off;  // [B+1]
-  const int32_t* na;     // [B] token counts of A / B (host-computed, they size the batch)
-  const int32_t* nb;
+  StrSample S;
   int32_t B, L;
   int64_t* input_ids;
   int64_t* token_type_ids;
   int64_t* attention_mask;
   int64_t* special_tokens_mask;  // dynamic masking (nullable)
-  // static masking (all nullable)
-  const uint8_t* lab_bytes;
-  const int64_t* lab_off;
-  const uint16_t* pos;
-  const int64_t* pos_off;
+  StrLabels G;
   int64_t* labels;
   int64_t* loss_mask;  // static masking (nullable): 1 at the sample's masked_lm_positions, else 0
   int64_t ignore_index;
@@ -76,9 +73,9 @@ encode_kernel(std::conditional_t<WW, EncodeWwArgs, EncodeArgs> E) {
   const bool active = b < E.B;
   int32_t* sid = srow + (size_t)w * 2 * E.L;
   int32_t* slab = sid + E.L;
-  const int32_t na = active ? E.na[b] : 0, nb = active ? E.nb[b] : 0;
+  const int32_t na = active ? E.S.na[b] : 0, nb = active ? E.S.nb[b] : 0;
   const int32_t end = na + nb + 3;
-  const int32_t cls = E.T.special_id[kCls], sep = E.T.special_id[kSep];
+  const int32_t cls = E.S.T.special_id[kCls], sep = E.S.T.special_id[kSep];
   if (active) {
     for (int32_t x = lane; x < E.L; x += 64) {
       if (x == 0) sid[x] = cls;
@@ -89,22 +86,23 @@ encode_kernel(std::conditional_t<WW, EncodeWwArgs, EncodeArgs> E) {
   }
   __syncthreads();
   if (active) {
-    split_lookup(E.T, E.bytes, E.a_off[b], E.a_off[b + 1], sid + 1, na, nullptr, E.L);
-    split_lookup(E.T, E.bytes, E.b_off[b], E.b_off[b + 1], sid + na + 2, nb, nullptr, E.L);
-    if (E.labels && E.lab_bytes) {  // labels[b, positions] = ids of masked_lm_labels (bert.py:120-125)
-      const int64_t p0 = E.pos_off[b];
-      const int32_t npos = (int32_t)(E.pos_off[b + 1] - p0);
+    split_lookup(E.S.T, E.S.bytes, E.S.a_off[b], E.S.a_off[b + 1], sid + 1, na, nullptr, E.L);
+    split_lookup(E.S.T, E.S.bytes, E.S.b_off[b], E.S.b_off[b + 1], sid + na + 2, nb, nullptr, E.L);
+    if (E.labels && E.G.lab_bytes) {  // labels[b, positions] = ids of masked_lm_labels (bert.py:120-125)
+      const int64_t p0 = E.G.pos_off[b];
+      const int32_t npos = (int32_t)(E.G.pos_off[b + 1] - p0);
       if (E.loss_mask) {
         // the loss mask follows the positions, not "a label was found": mark them -2 in the
         // labels row (still < 0 = ignore_index if the labels string is short). The label ids
         // land on the same LDS words from other lanes of this wave: marks first.
         for (int32_t k = lane; k < npos; k += 64) {
-          const int32_t p = E.pos[p0 + k];
+          const int32_t p = E.G.pos[p0 + k];
           if (p < E.L) slab[p] = -2;
         }
         wave_sync();
       }
-      split_lookup(E.T, E.lab_bytes, E.lab_off[b], E.lab_off[b + 1], slab, npos, E.pos + p0, E.L);
+      split_lookup(E.S.T, E.G.lab_bytes, E.G.lab_off[b], E.G.lab_off[b + 1], slab, npos,
+                   E.G.pos + p0, E.L);
     }
   }
   __syncthreads();
@@ -175,7 +173,7 @@ __device__ inline bool mask_special(const MaskArgs& M, int64_t i, int64_t b, int
   if (M.special) return M.special[i] != 0;
   if (M.na) {
     const int32_t na = M.na[b], end = na + M.nb[b] + 3;
-    return x == 0 || x == na + 1 || x >= end - 1;
+    return SlotLayout{na, end}.special(x);
   }
   bool sp = false;  // tokenizer.get_special_tokens_mask(ids, already_has_special_tokens=True)
   for (int k = 0; k < kNumSpecial; ++k) sp |= M.special_ids[k] >= 0 && id == M.special_ids[k];
@@ -248,17 +246,35 @@ static int collate_encode(lddl_ctx* c, void* stream, const uint8_t* d_bytes, con
                           const int64_t* d_lab_off, const uint16_t* d_pos, const int64_t* d_pos_off,
                           int64_t* d_labels, int64_t* d_loss_mask, int64_t ignore_index) {
   if (batch <= 0 || seq_len <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS] and [SEP]");
-  EncodeArgs E{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len, d_input_ids,
-               d_token_type_ids, d_attention_mask, d_special_tokens_mask, d_lab_bytes, d_lab_off,
-               d_pos, d_pos_off, d_labels, d_loss_mask, ignore_index, 0, {}};
-  const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;
-  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", seq_len);
-  hipLaunchKernelGGL(encode_kernel<false>, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
-                     dim3(64 * kEncWaves), lds, as_stream(stream), E);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  if (need_vocab(c, false)) return -1;
+  EncodeArgs E{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb}, batch, seq_len, d_input_ids,
+               d_token_type_ids, d_attention_mask, d_special_tokens_mask,
+               {d_lab_bytes, d_lab_off, d_pos, d_pos_off}, d_labels, d_loss_mask, ignore_index, 0,
+               {}};
+  return launch_rows(encode_kernel<false>, E, batch, 2, seq_len, stream);  // ids and labels
+}
+
+// lddl_collate_encode_masked and lddl_collate_encode_masked_ww
+static int collate_encode_masked(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
+                                 const int64_t* d_a_off, const int64_t* d_b_off,
+                                 const int32_t* d_na, const int32_t* d_nb, int32_t batch,
+                                 int32_t seq_len, int64_t* d_input_ids, int64_t* d_token_type_ids,
+                                 int64_t* d_attention_mask, int64_t* d_labels,
+                                 float mlm_probability, int64_t ignore_index, int64_t vocab_len,
+                                 uint64_t seed, uint64_t counter, bool whole_word) {
+  if (!c) LDDL_FAIL(-1, "null ctx");
+  if (batch <= 0 || seq_len <= 0) return 0;
+  if (need_vocab(c, true)) return -1;
+  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels)
+    LDDL_FAIL(-1, "null output");
+  const EncodeWwArgs E{{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb}, batch, seq_len,
+                        d_input_ids, d_token_type_ids, d_attention_mask, nullptr, {}, d_labels,
+                        nullptr, ignore_index, 1,
+                        mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter)},
+                       cont_bits_of(c)};
+  return whole_word
+             ? launch_rows(encode_kernel<true>, E, batch, 2, seq_len, stream)
+             : launch_rows(encode_kernel<false>, (const EncodeArgs&)E, batch, 2, seq_len, stream);
 }
 
 extern "C" int lddl_collate_encode(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
@@ -324,23 +340,9 @@ extern "C" int lddl_collate_encode_masked(lddl_ctx* c, void* stream, const uint8
                                           int64_t* d_labels, float mlm_probability,
                                           int64_t ignore_index, int64_t vocab_len, uint64_t seed,
                                           uint64_t counter) {
-  if (!c) LDDL_FAIL(-1, "null ctx");
-  if (batch <= 0 || seq_len <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0 || c->tab.special_id[kMask] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS], [SEP] and [MASK]");
-  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels)
-    LDDL_FAIL(-1, "null output");
-  EncodeArgs E{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len, d_input_ids,
-               d_token_type_ids, d_attention_mask, nullptr, nullptr, nullptr, nullptr, nullptr,
-               d_labels, nullptr, ignore_index, 1,
-               MaskDraw{mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, seed,
-                        counter}};
-  const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;
-  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", seq_len);
-  hipLaunchKernelGGL(encode_kernel<false>, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
-                     dim3(64 * kEncWaves), lds, as_stream(stream), E);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  return collate_encode_masked(c, stream, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len,
+                               d_input_ids, d_token_type_ids, d_attention_mask, d_labels,
+                               mlm_probability, ignore_index, vocab_len, seed, counter, false);
 }
 
 extern "C" int lddl_mask_dynamic_ww(lddl_ctx* c, void* stream, int64_t* d_input_ids,
@@ -358,7 +360,7 @@ extern "C" int lddl_mask_dynamic_ww(lddl_ctx* c, void* stream, int64_t* d_input_
   for (int k = 0; k < kNumSpecial; ++k) M.special_ids[k] = c->tab.special_id[k];
   hipLaunchKernelGGL(mask_ww_kernel, dim3((unsigned)((batch + kWwWaves - 1) / kWwWaves)),
                      dim3(64 * kWwWaves), 0, as_stream(stream), M,
-                     ContBits{c->d_cont_bits, c->vocab_size});
+                     cont_bits_of(c));
   LDDL_HIP(hipGetLastError());
   return 0;
 }
@@ -371,22 +373,7 @@ extern "C" int lddl_collate_encode_masked_ww(lddl_ctx* c, void* stream, const ui
                                              int64_t* d_labels, float mlm_probability,
                                              int64_t ignore_index, int64_t vocab_len, uint64_t seed,
                                              uint64_t counter) {
-  if (!c) LDDL_FAIL(-1, "null ctx");
-  if (batch <= 0 || seq_len <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0 || c->tab.special_id[kMask] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS], [SEP] and [MASK]");
-  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels)
-    LDDL_FAIL(-1, "null output");
-  EncodeWwArgs E{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len, d_input_ids,
-                  d_token_type_ids, d_attention_mask, nullptr, nullptr, nullptr, nullptr, nullptr,
-                  d_labels, nullptr, ignore_index, 1,
-                  MaskDraw{mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len,
-                           seed, counter}},
-                 ContBits{c->d_cont_bits, c->vocab_size}};
-  const size_t lds = sizeof(int32_t) * 2 * (size_t)seq_len * kEncWaves;
-  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", seq_len);
-  hipLaunchKernelGGL(encode_kernel<true>, dim3((unsigned)((batch + kEncWaves - 1) / kEncWaves)),
-                     dim3(64 * kEncWaves), lds, as_stream(stream), E);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  return collate_encode_masked(c, stream, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, seq_len,
+                               d_input_ids, d_token_type_ids, d_attention_mask, d_labels,
+                               mlm_probability, ignore_index, vocab_len, seed, counter, true);
 }

@@ -1,6 +1,10 @@
-// Device helpers shared by the collate kernels (collate.hip, collate_seqpack.hip): the exact
-// vocab lookup of a whitespace-split string, the per-slot Philox masking decision and the
-// whole-word ballot. Each translation unit gets its own copy (anonymous namespace).
+// Device helpers shared by the collate kernels (collate.hip, collate_seqpack.hip,
+// collate_pairs.hip, collate_pairs_seqpack.hip): the exact vocab lookup of a whitespace-split
+// string, the per-slot Philox masking decision and the whole-word ballot, the MODE enum, the
+// slot layout of a sample (SlotLayout), the arguments of a string sample (StrSample, StrLabels)
+// and the read side of a pair table (PairTable, load_id, PairSlots, scatter_labels). The
+// kernels keep their loops and stores. The host side of the same units is collate_host.h.
+// Each translation unit gets its own copy (anonymous namespace).
 #pragma once
 #include "common.h"
 #include "ctx.h"
@@ -124,6 +128,98 @@ __device__ inline bool word_masked(bool head, bool own, int lane, bool& carry) {
 
 // waves (= samples) per block of the collate kernels that stage a row in LDS
 constexpr int kEncWaves = 4;
+
+// what a collate kernel does on the way out: nothing (unmasked or static labels), the fused
+// per-token dynamic masking, or the fused whole-word one
+enum { kPlain = 0, kFused = 1, kFusedWw = 2 };
+
+// The slots of one sample, [CLS] A [SEP] B [SEP] and padding behind: na tokens of A, end =
+// na + nb + 3 slots in all. X is the caller's slot type (int32_t, or int64_t in mask_kernel).
+// The layout refers to the caller's na and end, as a [&] lambda would, and does not copy them:
+// with copies the compiler promotes the values in another order and the kernels' code changes
+// (DESIGN §21). The string kernels and the whole-word loops write the predicates out for the
+// same reason.
+struct SlotLayout {
+  const int32_t& na;
+  const int32_t& end;
+  template <typename X>
+  __device__ bool special(X x) const { return x == 0 || x == na + 1 || x >= end - 1; }
+  template <typename X>
+  __device__ bool is_sep(X x) const { return x == na + 1 || x == end - 1; }
+  template <typename X>
+  __device__ bool real(X x) const { return x < end; }
+  template <typename X>
+  __device__ int64_t segment(X x) const { return (x >= na + 2 && x < end) ? 1 : 0; }  // token type
+};
+
+// ---- the string read side (collate.hip, collate_seqpack.hip) ---------------------------------
+// Two structs, not one: they sit in EncodeArgs and SeqpackArgs where their fields sat, so the
+// kernels read their arguments at the offsets they had.
+struct StrSample {
+  Tables T;
+  const uint8_t* bytes;
+  const int64_t* a_off;  // [B+1] A string of sample b = bytes[a_off[b], a_off[b+1])
+  const int64_t* b_off;  // [B+1]
+  const int32_t* na;     // [B] token counts of A / B (host-computed, they size the batch)
+  const int32_t* nb;
+};
+struct StrLabels {  // static masking (all nullable)
+  const uint8_t* lab_bytes;
+  const int64_t* lab_off;
+  const uint16_t* pos;
+  const int64_t* pos_off;
+};
+
+// ---- the pair-table read side (collate_pairs.hip, collate_pairs_seqpack.hip) -----------------
+struct PairTable {
+  const void* tokens;      // uint16 or int32 ids
+  const int64_t* tok_off;  // [n_pairs + 1]
+  const int32_t* len_a;
+  const uint8_t* is_rn;
+  // static masking (all or none)
+  const uint16_t* pos;
+  const void* lab;
+  const int64_t* pos_off;
+  const int64_t* rows;  // nullable: identity
+};
+
+template <typename ID>
+__device__ inline int32_t load_id(const void* p, int64_t i) {
+  return (int32_t) reinterpret_cast<const ID*>(p)[i];
+}
+
+// The id of slot x before masking, of the pair whose tokens start at t0. Like SlotLayout it
+// refers to the caller's values, as a [&] lambda would.
+template <typename ID>
+struct PairSlots {
+  const PairTable& P;
+  const int64_t& t0;
+  const SlotLayout& lay;
+  const int32_t& cls;
+  const int32_t& sep;
+  __device__ int32_t operator()(int32_t x) const {
+    if (x == 0) return cls;
+    if (lay.is_sep(x)) return sep;
+    if (x >= lay.end) return 0;
+    return load_id<ID>(P.tokens, t0 + x - (x <= lay.na ? 1 : 2));
+  }
+};
+
+// slab[0, limit) = the static label of pair q's slot or -1, one wave; a position >= limit is
+// dropped
+template <typename ID>
+__device__ inline void scatter_labels(const PairTable& P, int64_t q, int32_t* slab, int32_t limit,
+                                      int lane) {
+  for (int32_t x = lane; x < limit; x += 64) slab[x] = -1;
+  wave_sync();
+  const int64_t p0 = P.pos_off[q];
+  const int32_t npos = (int32_t)(P.pos_off[q + 1] - p0);
+  for (int32_t k = lane; k < npos; k += 64) {
+    const int32_t p = P.pos[p0 + k];
+    if (p < limit) slab[p] = load_id<ID>(P.lab, p0 + k);
+  }
+  wave_sync();
+}
 
 }  // namespace
 }  // namespace lddl

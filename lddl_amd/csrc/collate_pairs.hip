@@ -9,9 +9,11 @@
 //     na + 2 <= x < end - 1   tokens[tok_off[q] + x - 2]  (B)
 //     x == end - 1      [SEP]            end = na + nb + 3
 //     x >= end          0 (padding)
-// and the masking decision of a slot is collate_dev.h's (MaskDraw, mask_draw, mask_apply,
-// word_masked, ContBits), with the same Philox index i * seq_len + x: the mask stream is the
-// string kernels' by construction.
+// which is collate_dev.h's PairSlots over its SlotLayout, shared with pack_kernel like the label
+// scatter (scatter_labels); the masking decision of a slot is collate_dev.h's too (MaskDraw,
+// mask_draw, mask_apply, word_masked, ContBits), with the same Philox index i * seq_len + x: the
+// mask stream is the string kernels' by construction. This unit owns the three row loops and
+// their stores; the whole-word loop writes its two predicates out (collate_dev.h says why).
 //
 //   lddl_collate_pairs          lddl_collate_encode: unmasked (special_tokens_mask) or static
 //                               (labels scattered from pos / labels through one LDS row per wave,
@@ -20,7 +22,7 @@
 //
 // One wave per output row, kEncWaves rows per block; all offsets 64-bit (a table holds more than
 // 2^31 tokens); both id widths of lddl_ctx_id_bytes().
-#include "collate_dev.h"  // MaskDraw ..., ContBits, word_masked, kEncWaves
+#include "collate_host.h"  // need_vocab, need_static_triple, launch_rows; collate_dev.h
 #include "common.h"
 #include "ctx.h"
 #include "device.h"
@@ -29,18 +31,8 @@
 namespace lddl {
 namespace {
 
-enum { kPlain = 0, kFused = 1, kFusedWw = 2 };
-
 struct PairsArgs {
-  const void* tokens;      // uint16 or int32 ids
-  const int64_t* tok_off;  // [n_pairs + 1]
-  const int32_t* len_a;
-  const uint8_t* is_rn;
-  // static masking (all or none)
-  const uint16_t* pos;
-  const void* lab;
-  const int64_t* pos_off;
-  const int64_t* rows;  // nullable: identity
+  PairTable P;
   int32_t B, L;
   int32_t cls, sep;
   int64_t* input_ids;
@@ -54,32 +46,22 @@ struct PairsArgs {
   ContBits cont;
 };
 
-template <typename ID>
-__device__ inline int32_t load_id(const void* p, int64_t i) {
-  return (int32_t) reinterpret_cast<const ID*>(p)[i];
-}
-
 template <typename ID, int MODE>
 __global__ void __launch_bounds__(64 * kEncWaves) pairs_kernel(PairsArgs E) {
   extern __shared__ __attribute__((aligned(16))) int32_t srow[];  // static masking: [waves][L]
   const int w = wave_id(), lane = threadIdx.x & 63;
   const int32_t b = blockIdx.x * kEncWaves + w;
   if (b >= E.B) return;  // the whole wave; no block-wide barrier below
-  const int64_t q = E.rows ? E.rows[b] : (int64_t)b;
-  const int64_t t0 = E.tok_off[q];
-  const int32_t na = E.len_a[q];
-  const int32_t nb = (int32_t)(E.tok_off[q + 1] - t0) - na;
+  const int64_t q = E.P.rows ? E.P.rows[b] : (int64_t)b;
+  const int64_t t0 = E.P.tok_off[q];
+  const int32_t na = E.P.len_a[q];
+  const int32_t nb = (int32_t)(E.P.tok_off[q + 1] - t0) - na;
   const int32_t end = na + nb + 3;
+  const SlotLayout lay{na, end};
   const int64_t row = (int64_t)b * E.L;
-  if (lane == 0) E.nsl[b] = E.is_rn[q] ? 1 : 0;
+  if (lane == 0) E.nsl[b] = E.P.is_rn[q] ? 1 : 0;
 
-  // the slot's id before masking (x < L)
-  auto slot_id = [&](int32_t x) -> int32_t {
-    if (x == 0) return E.cls;
-    if (x == na + 1 || x == end - 1) return E.sep;
-    if (x >= end) return 0;
-    return load_id<ID>(E.tokens, t0 + x - (x <= na ? 1 : 2));
-  };
+  const PairSlots<ID> slot_id{E.P, t0, lay, E.cls, E.sep};  // the id before masking (x < L)
 
   if constexpr (MODE == kFusedWw) {
     // windows of 64 slots up to a multiple of 64, the tail predicated: every lane reaches the
@@ -98,57 +80,42 @@ __global__ void __launch_bounds__(64 * kEncWaves) pairs_kernel(PairsArgs E) {
         int64_t lab;
         E.input_ids[row + x] = mask_apply(E.draw, r, !special && m, id, &lab);
         E.labels[row + x] = lab;
-        E.token_type_ids[row + x] = (x >= na + 2 && x < end) ? 1 : 0;
-        E.attention_mask[row + x] = x < end ? 1 : 0;
+        E.token_type_ids[row + x] = lay.segment(x);
+        E.attention_mask[row + x] = lay.real(x) ? 1 : 0;
       }
     }
     return;
   } else if constexpr (MODE == kFused) {
     for (int32_t x = lane; x < E.L; x += 64) {
-      const bool special = x == 0 || x == na + 1 || x >= end - 1;
+      const bool special = lay.special(x);
       const uint4 r = mask_draw(E.draw, row + x);
       int64_t lab;
-      E.input_ids[row + x] =
-          mask_apply(E.draw, r, !special && u01(r.x) < E.draw.p, slot_id(x), &lab);
+      E.input_ids[row + x] = mask_apply(E.draw, r, !special && u01(r.x) < E.draw.p,
+                                        slot_id(x), &lab);
       E.labels[row + x] = lab;
-      E.token_type_ids[row + x] = (x >= na + 2 && x < end) ? 1 : 0;
-      E.attention_mask[row + x] = x < end ? 1 : 0;
+      E.token_type_ids[row + x] = lay.segment(x);
+      E.attention_mask[row + x] = lay.real(x) ? 1 : 0;
     }
     return;
   } else {
     int32_t* slab = srow + (size_t)w * E.L;
-    if (E.pos) {  // labels[b, positions] = the pair's label ids; a position >= L is dropped
-      for (int32_t x = lane; x < E.L; x += 64) slab[x] = -1;
-      wave_sync();
-      const int64_t p0 = E.pos_off[q];
-      const int32_t npos = (int32_t)(E.pos_off[q + 1] - p0);
-      for (int32_t k = lane; k < npos; k += 64) {
-        const int32_t p = E.pos[p0 + k];
-        if (p < E.L) slab[p] = load_id<ID>(E.lab, p0 + k);
-      }
-      wave_sync();
-    }
+    // labels[b, positions] = the pair's label ids; a position >= L is dropped
+    if (E.P.pos) scatter_labels<ID>(E.P, q, slab, E.L, lane);
     for (int32_t x = lane; x < E.L; x += 64) {
       E.input_ids[row + x] = slot_id(x);
-      E.token_type_ids[row + x] = (x >= na + 2 && x < end) ? 1 : 0;
-      E.attention_mask[row + x] = x < end ? 1 : 0;
-      if (E.pos) E.labels[row + x] = slab[x] < 0 ? E.ignore_index : (int64_t)slab[x];
-      else E.special_tokens_mask[row + x] = (x == 0 || x == na + 1 || x >= end - 1) ? 1 : 0;
+      E.token_type_ids[row + x] = lay.segment(x);
+      E.attention_mask[row + x] = lay.real(x) ? 1 : 0;
+      if (E.P.pos) E.labels[row + x] = slab[x] < 0 ? E.ignore_index : (int64_t)slab[x];
+      else E.special_tokens_mask[row + x] = lay.special(x) ? 1 : 0;
     }
   }
 }
 
 template <int MODE>
 int launch(lddl_ctx* c, const PairsArgs& E, void* stream) {
-  const size_t lds = (MODE == kPlain && E.pos) ? sizeof(int32_t) * (size_t)E.L * kEncWaves : 0;
-  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", E.L);
-  const dim3 grid((unsigned)((E.B + kEncWaves - 1) / kEncWaves)), block(64 * kEncWaves);
-  if (c->id_bytes() == 2)
-    hipLaunchKernelGGL((pairs_kernel<uint16_t, MODE>), grid, block, lds, as_stream(stream), E);
-  else
-    hipLaunchKernelGGL((pairs_kernel<int32_t, MODE>), grid, block, lds, as_stream(stream), E);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  const int words = (MODE == kPlain && E.P.pos) ? 1 : 0;
+  return c->id_bytes() == 2 ? launch_rows(pairs_kernel<uint16_t, MODE>, E, E.B, words, E.L, stream)
+                            : launch_rows(pairs_kernel<int32_t, MODE>, E, E.B, words, E.L, stream);
 }
 
 }  // namespace
@@ -166,16 +133,14 @@ extern "C" int lddl_collate_pairs(lddl_ctx* c, void* stream, const void* d_token
                                   int64_t ignore_index) {
   if (!c) LDDL_FAIL(-1, "null ctx");
   if (batch <= 0 || seq_len <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS] and [SEP]");
+  if (need_vocab(c, false)) return -1;
   if (!d_tokens || !d_tok_off || !d_len_a || !d_is_rn) LDDL_FAIL(-1, "null pair table");
   const bool is_static = d_pos != nullptr;
-  if ((d_lab != nullptr) != is_static || (d_pos_off != nullptr) != is_static)
-    LDDL_FAIL(-1, "static masking needs pos, labels and pos_off, all three or none");
+  if (need_static_triple(d_pos, d_lab, d_pos_off)) return -1;
   if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_next_sentence_labels ||
       (is_static ? !d_labels : !d_special_tokens_mask))
     LDDL_FAIL(-1, "null output");
-  PairsArgs E{d_tokens, d_tok_off, d_len_a, d_is_rn, d_pos, d_lab, d_pos_off, d_rows, batch,
+  PairsArgs E{{d_tokens, d_tok_off, d_len_a, d_is_rn, d_pos, d_lab, d_pos_off, d_rows}, batch,
               seq_len, c->tab.special_id[kCls], c->tab.special_id[kSep], d_input_ids,
               d_token_type_ids, d_attention_mask, d_special_tokens_mask, d_labels,
               d_next_sentence_labels, ignore_index, {}, {}};
@@ -193,18 +158,16 @@ extern "C" int lddl_collate_pairs_masked(lddl_ctx* c, void* stream, const void* 
                                          int32_t whole_word) {
   if (!c) LDDL_FAIL(-1, "null ctx");
   if (batch <= 0 || seq_len <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0 || c->tab.special_id[kMask] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS], [SEP] and [MASK]");
+  if (need_vocab(c, true)) return -1;
   if (!d_tokens || !d_tok_off || !d_len_a || !d_is_rn) LDDL_FAIL(-1, "null pair table");
   if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels ||
       !d_next_sentence_labels)
     LDDL_FAIL(-1, "null output");
-  PairsArgs E{d_tokens, d_tok_off, d_len_a, d_is_rn, nullptr, nullptr, nullptr, d_rows, batch,
+  PairsArgs E{{d_tokens, d_tok_off, d_len_a, d_is_rn, nullptr, nullptr, nullptr, d_rows}, batch,
               seq_len, c->tab.special_id[kCls], c->tab.special_id[kSep], d_input_ids,
               d_token_type_ids, d_attention_mask, nullptr, d_labels, d_next_sentence_labels,
               ignore_index,
-              MaskDraw{mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, seed,
-                       counter},
-              ContBits{c->d_cont_bits, c->vocab_size}};
+              mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
+              cont_bits_of(c)};
   return whole_word ? launch<kFusedWw>(c, E, stream) : launch<kFused>(c, E, stream);
 }

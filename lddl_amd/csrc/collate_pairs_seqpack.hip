@@ -8,7 +8,10 @@
 //     na + 2 <= x < len - 1   tokens[tok_off[q] + x - 2]  (B)
 //     x == len - 1      [SEP]            len = na + nb + 3
 // plus position_ids = x and sequence_ids = seq_in_row[i]; slots [len, fill) are the row's tail:
-// 0 everywhere, labels ignore_index, special_tokens_mask 1. The segments tile the outputs, so
+// 0 everywhere, labels ignore_index, special_tokens_mask 1. The slot's id, the layout and the
+// label scatter are collate_dev.h's (PairSlots, SlotLayout, scatter_labels), shared with
+// pairs_kernel; this unit owns the plan's prologue, the predicated window loop and its stores.
+// The segments tile the outputs, so
 // every element is written once and nothing is cleared beforehand. The per-sample outputs
 // (next_sentence_labels, cls_positions, seq_lens) are written by the sample's wave at
 // packed_idx[i], its place in (row, start) order.
@@ -23,7 +26,7 @@
 //
 // One wave per sample, kEncWaves per block; all offsets 64-bit; both id widths of
 // lddl_ctx_id_bytes().
-#include "collate_dev.h"  // MaskDraw ..., ContBits, word_masked, kEncWaves
+#include "collate_host.h"  // need_vocab, need_static_triple, launch_rows; collate_dev.h
 #include "common.h"
 #include "ctx.h"
 #include "device.h"
@@ -32,18 +35,8 @@
 namespace lddl {
 namespace {
 
-enum { kPlain = 0, kFused = 1, kFusedWw = 2 };
-
 struct PackArgs {
-  const void* tokens;      // uint16 or int32 ids
-  const int64_t* tok_off;  // [n_pairs + 1]
-  const int32_t* len_a;
-  const uint8_t* is_rn;
-  // static masking (all or none)
-  const uint16_t* pos;
-  const void* lab;
-  const int64_t* pos_off;
-  const int64_t* rows;  // nullable: identity
+  PairTable P;
   // the plan, [B] each
   const int64_t* dst;
   const int32_t* fill;
@@ -67,11 +60,6 @@ struct PackArgs {
   ContBits cont;
 };
 
-template <typename ID>
-__device__ inline int32_t load_id(const void* p, int64_t i) {
-  return (int32_t) reinterpret_cast<const ID*>(p)[i];
-}
-
 template <typename ID, int MODE>
 __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
   extern __shared__ __attribute__((aligned(16))) int32_t srow[];  // static masking: [waves][L]
@@ -80,15 +68,15 @@ __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
   if (b >= E.B) return;  // the whole wave; no block-wide barrier below
   // every load of the prologue is issued before the first wait: the plan's four words beside
   // rows[b], the table's beside each other (two round trips, as in pairs_kernel)
-  const int64_t q = E.rows ? E.rows[b] : (int64_t)b;
+  const int64_t q = E.P.rows ? E.P.rows[b] : (int64_t)b;
   const int64_t o = E.dst[b];
   const int32_t fill = E.fill[b];
   const int32_t at = E.packed_idx[b];
   const int64_t seq = E.seq_in_row[b];
-  const int64_t t0 = E.tok_off[q];
-  const int32_t na = E.len_a[q];
-  const int32_t nb = (int32_t)(E.tok_off[q + 1] - t0) - na;
-  const bool rn = E.is_rn[q] != 0;
+  const int64_t t0 = E.P.tok_off[q];
+  const int32_t na = E.P.len_a[q];
+  const int32_t nb = (int32_t)(E.P.tok_off[q + 1] - t0) - na;
+  const bool rn = E.P.is_rn[q] != 0;
   const int32_t end = na + nb + 3;
   // a sample that takes no row (dst = -1: longer than a row, refused on the host) and a plan
   // that is not this batch's write nothing: no slot outside the outputs is ever touched. One
@@ -98,29 +86,13 @@ __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
       (o + fill > (int64_t)E.R * E.L) | (at < 0) | (at >= E.B) | (seq < 1))
     return;
   const int64_t flat = (int64_t)b * E.draw_stride;
-
-  // the slot's id before masking (x < fill)
-  auto slot_id = [&](int32_t x) -> int32_t {
-    if (x == 0) return E.cls;
-    if (x == na + 1 || x == end - 1) return E.sep;
-    if (x >= end) return 0;
-    return load_id<ID>(E.tokens, t0 + x - (x <= na ? 1 : 2));
-  };
+  const SlotLayout lay{na, end};
+  const PairSlots<ID> slot_id{E.P, t0, lay, E.cls, E.sep};  // the id before masking (x < fill)
 
   int32_t* slab = srow + (size_t)w * E.L;
-  if (MODE == kPlain && E.pos) {
-    // positions count from the sample's [CLS]; one at or past its end would land in the next
-    // sample (refused on the host, dropped here)
-    for (int32_t x = lane; x < end; x += 64) slab[x] = -1;
-    wave_sync();
-    const int64_t p0 = E.pos_off[q];
-    const int32_t npos = (int32_t)(E.pos_off[q + 1] - p0);
-    for (int32_t k = lane; k < npos; k += 64) {
-      const int32_t p = E.pos[p0 + k];
-      if (p < end) slab[p] = load_id<ID>(E.lab, p0 + k);
-    }
-    wave_sync();
-  }
+  // positions count from the sample's [CLS]; one at or past its end would land in the next
+  // sample (refused on the host, dropped here)
+  if (MODE == kPlain && E.P.pos) scatter_labels<ID>(E.P, q, slab, end, lane);
 
   // 64-slot windows from the sample's start, the tail predicated: with MODE == kFusedWw every
   // lane reaches the ballots of word_masked
@@ -128,7 +100,7 @@ __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
   for (int32_t x0 = 0; x0 < fill; x0 += 64) {
     const int32_t x = x0 + lane;
     const bool in = x < fill, real = x < end;
-    const bool special = x == 0 || x == na + 1 || x >= end - 1;
+    const bool special = lay.special(x);
     const int32_t id = in ? slot_id(x) : 0;
     int64_t out = id, lab = E.ignore_index;
     if constexpr (MODE == kFusedWw) {
@@ -140,7 +112,7 @@ __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
     } else if constexpr (MODE == kFused) {
       if (real) out = mask_slot(E.draw, flat + x, special, id, &lab);
     } else {
-      if (E.pos && real && slab[x] >= 0) lab = slab[x];
+      if (E.P.pos && real && slab[x] >= 0) lab = slab[x];
     }
     if (in) {
       E.input_ids[o + x] = out;
@@ -148,7 +120,7 @@ __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
       E.attention_mask[o + x] = real ? 1 : 0;
       E.position_ids[o + x] = real ? x : 0;
       E.sequence_ids[o + x] = real ? seq : 0;
-      if (MODE != kPlain || E.pos) E.labels[o + x] = lab;
+      if (MODE != kPlain || E.P.pos) E.labels[o + x] = lab;
       else E.special_tokens_mask[o + x] = special ? 1 : 0;
     }
   }
@@ -161,15 +133,9 @@ __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
 
 template <int MODE>
 int launch(lddl_ctx* c, const PackArgs& E, void* stream) {
-  const size_t lds = (MODE == kPlain && E.pos) ? sizeof(int32_t) * (size_t)E.L * kEncWaves : 0;
-  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", E.L);
-  const dim3 grid((unsigned)((E.B + kEncWaves - 1) / kEncWaves)), block(64 * kEncWaves);
-  if (c->id_bytes() == 2)
-    hipLaunchKernelGGL((pack_kernel<uint16_t, MODE>), grid, block, lds, as_stream(stream), E);
-  else
-    hipLaunchKernelGGL((pack_kernel<int32_t, MODE>), grid, block, lds, as_stream(stream), E);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  const int words = (MODE == kPlain && E.P.pos) ? 1 : 0;
+  return c->id_bytes() == 2 ? launch_rows(pack_kernel<uint16_t, MODE>, E, E.B, words, E.L, stream)
+                            : launch_rows(pack_kernel<int32_t, MODE>, E, E.B, words, E.L, stream);
 }
 
 }  // namespace
@@ -188,19 +154,17 @@ extern "C" int lddl_collate_pairs_seqpack(
     int64_t* d_cls_positions, int32_t* d_seq_lens, int64_t ignore_index) {
   if (!c) LDDL_FAIL(-1, "null ctx");
   if (batch <= 0 || out_rows <= 0 || max_seq_length <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS] and [SEP]");
+  if (need_vocab(c, false)) return -1;
   if (!d_tokens || !d_tok_off || !d_len_a || !d_is_rn) LDDL_FAIL(-1, "null pair table");
   if (!d_dst || !d_fill || !d_seq_in_row || !d_packed_idx) LDDL_FAIL(-1, "null plan");
   const bool is_static = d_pos != nullptr;
-  if ((d_lab != nullptr) != is_static || (d_pos_off != nullptr) != is_static)
-    LDDL_FAIL(-1, "static masking needs pos, labels and pos_off, all three or none");
+  if (need_static_triple(d_pos, d_lab, d_pos_off)) return -1;
   if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_position_ids ||
       !d_sequence_ids || !d_next_sentence_labels || !d_cls_positions || !d_seq_lens ||
       (is_static ? !d_labels : !d_special_tokens_mask))
     LDDL_FAIL(-1, "null output");
-  PackArgs E{d_tokens, d_tok_off, d_len_a, d_is_rn, d_pos, d_lab, d_pos_off, d_rows, d_dst, d_fill,
-             d_seq_in_row, d_packed_idx, batch, out_rows, max_seq_length, 0,
+  PackArgs E{{d_tokens, d_tok_off, d_len_a, d_is_rn, d_pos, d_lab, d_pos_off, d_rows}, d_dst,
+             d_fill, d_seq_in_row, d_packed_idx, batch, out_rows, max_seq_length, 0,
              c->tab.special_id[kCls], c->tab.special_id[kSep], d_input_ids, d_token_type_ids,
              d_attention_mask, d_special_tokens_mask, d_labels, d_position_ids, d_sequence_ids,
              d_next_sentence_labels, d_cls_positions, d_seq_lens, ignore_index, {}, {}};
@@ -218,20 +182,18 @@ extern "C" int lddl_collate_pairs_seqpack_masked(
     int64_t vocab_len, uint64_t seed, uint64_t counter, int32_t whole_word) {
   if (!c) LDDL_FAIL(-1, "null ctx");
   if (batch <= 0 || out_rows <= 0 || max_seq_length <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0 || c->tab.special_id[kMask] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS], [SEP] and [MASK]");
+  if (need_vocab(c, true)) return -1;
   if (!d_tokens || !d_tok_off || !d_len_a || !d_is_rn) LDDL_FAIL(-1, "null pair table");
   if (!d_dst || !d_fill || !d_seq_in_row || !d_packed_idx) LDDL_FAIL(-1, "null plan");
   if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels || !d_position_ids ||
       !d_sequence_ids || !d_next_sentence_labels || !d_cls_positions || !d_seq_lens)
     LDDL_FAIL(-1, "null output");
-  PackArgs E{d_tokens, d_tok_off, d_len_a, d_is_rn, nullptr, nullptr, nullptr, d_rows, d_dst,
+  PackArgs E{{d_tokens, d_tok_off, d_len_a, d_is_rn, nullptr, nullptr, nullptr, d_rows}, d_dst,
              d_fill, d_seq_in_row, d_packed_idx, batch, out_rows, max_seq_length, draw_stride,
              c->tab.special_id[kCls], c->tab.special_id[kSep], d_input_ids, d_token_type_ids,
              d_attention_mask, nullptr, d_labels, d_position_ids, d_sequence_ids,
              d_next_sentence_labels, d_cls_positions, d_seq_lens, ignore_index,
-             MaskDraw{mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, seed,
-                      counter},
-             ContBits{c->d_cont_bits, c->vocab_size}};
+             mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
+             cont_bits_of(c)};
   return whole_word ? launch<kFusedWw>(c, E, stream) : launch<kFused>(c, E, stream);
 }

@@ -9,21 +9,18 @@
 // [dst[i], dst[i] + fill[i]) of the [R, L] outputs, its tokens first and, for the last sample of
 // a row, the row's unused tail behind them. The segments tile the outputs, so every element is
 // written exactly once and nothing is cleared beforehand. One wave per sample, the segment
-// staged in LDS as in encode_kernel. The Philox index of slot x of sample i is
+// staged in LDS as in encode_kernel, whose string-side arguments it shares (collate_dev.h's
+// StrSample, StrLabels); the staging and the window loop are written out here, as the comment
+// at collate_dev.h's SlotLayout explains. The Philox index of slot x of sample i is
 // i * draw_stride + x: the masking is that of the unpacked batch, whatever the layout.
-#include "collate_dev.h"
+#include "collate_host.h"  // need_vocab, launch_rows; collate_dev.h
 #include "lddl_amd.h"
 
 namespace lddl {
 namespace {
 
 struct SeqpackArgs {
-  Tables T;
-  const uint8_t* bytes;
-  const int64_t* a_off;  // [B+1] A string of sample b = bytes[a_off[b], a_off[b+1])
-  const int64_t* b_off;  // [B+1]
-  const int32_t* na;     // [B]
-  const int32_t* nb;
+  StrSample S;
   const int64_t* dst;         // [B] flat slot row * L + start of the sample's [CLS]
   const int32_t* fill;        // [B] slots the sample's wave writes (>= na + nb + 3)
   const int32_t* seq_in_row;  // [B] 1-based
@@ -35,32 +32,26 @@ struct SeqpackArgs {
   int64_t* sequence_ids;
   int64_t* labels;               // static or fused masking, else null
   int64_t* special_tokens_mask;  // dynamic unmasked, else null
-  // static masking (all nullable)
-  const uint8_t* lab_bytes;
-  const int64_t* lab_off;
-  const uint16_t* pos;
-  const int64_t* pos_off;
+  StrLabels G;
   int64_t ignore_index;
   int32_t draw_stride;
   MaskDraw draw;
   ContBits cont;
 };
 
-enum { kPlain = 0, kFused = 1, kFusedWw = 2 };
-
 template <int MODE>
 __global__ void __launch_bounds__(64 * kEncWaves) seqpack_kernel(SeqpackArgs E) {
   extern __shared__ __attribute__((aligned(16))) int32_t srow[];
   const int w = wave_id(), lane = threadIdx.x & 63;
   const int b = blockIdx.x * kEncWaves + w;
-  const int32_t na = b < E.B ? E.na[b] : 0, nb = b < E.B ? E.nb[b] : 0;
+  const int32_t na = b < E.B ? E.S.na[b] : 0, nb = b < E.B ? E.S.nb[b] : 0;
   const int32_t end = na + nb + 3;
   // a sample that does not fit its row is refused on the host; here it must not leave the LDS
   const bool active = b < E.B && end <= E.L;
   const int32_t fill = active ? min(E.fill[b], E.L) : 0;
   int32_t* sid = srow + (size_t)w * 2 * E.L;
   int32_t* slab = sid + E.L;
-  const int32_t cls = E.T.special_id[kCls], sep = E.T.special_id[kSep];
+  const int32_t cls = E.S.T.special_id[kCls], sep = E.S.T.special_id[kSep];
   for (int32_t x = lane; x < fill; x += 64) {
     if (x == 0) sid[x] = cls;
     else if (x == na + 1 || x == end - 1) sid[x] = sep;
@@ -69,14 +60,14 @@ __global__ void __launch_bounds__(64 * kEncWaves) seqpack_kernel(SeqpackArgs E) 
   }
   __syncthreads();
   if (active) {
-    split_lookup(E.T, E.bytes, E.a_off[b], E.a_off[b + 1], sid + 1, na, nullptr, E.L);
-    split_lookup(E.T, E.bytes, E.b_off[b], E.b_off[b + 1], sid + na + 2, nb, nullptr, E.L);
-    if (MODE == kPlain && E.lab_bytes) {
+    split_lookup(E.S.T, E.S.bytes, E.S.a_off[b], E.S.a_off[b + 1], sid + 1, na, nullptr, E.L);
+    split_lookup(E.S.T, E.S.bytes, E.S.b_off[b], E.S.b_off[b + 1], sid + na + 2, nb, nullptr, E.L);
+    if (MODE == kPlain && E.G.lab_bytes) {
       // positions count from the sample's [CLS]; one at or past its end would land in the next
       // sample (refused on the host, dropped here)
-      const int64_t p0 = E.pos_off[b];
-      split_lookup(E.T, E.lab_bytes, E.lab_off[b], E.lab_off[b + 1], slab,
-                   (int32_t)(E.pos_off[b + 1] - p0), E.pos + p0, end);
+      const int64_t p0 = E.G.pos_off[b];
+      split_lookup(E.S.T, E.G.lab_bytes, E.G.lab_off[b], E.G.lab_off[b + 1], slab,
+                   (int32_t)(E.G.pos_off[b + 1] - p0), E.G.pos + p0, end);
     }
   }
   __syncthreads();
@@ -118,12 +109,7 @@ __global__ void __launch_bounds__(64 * kEncWaves) seqpack_kernel(SeqpackArgs E) 
 
 template <int MODE>
 int launch(const SeqpackArgs& E, void* stream) {
-  const size_t lds = sizeof(int32_t) * 2 * (size_t)E.L * kEncWaves;
-  if (lds > 160 * 1024) LDDL_FAIL(-1, "sequence length %d too long for the collate kernel", E.L);
-  hipLaunchKernelGGL(seqpack_kernel<MODE>, dim3((unsigned)((E.B + kEncWaves - 1) / kEncWaves)),
-                     dim3(64 * kEncWaves), lds, as_stream(stream), E);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  return launch_rows(seqpack_kernel<MODE>, E, E.B, 2, E.L, stream);  // ids and labels
 }
 
 }  // namespace
@@ -144,8 +130,7 @@ extern "C" int lddl_collate_seqpack(lddl_ctx* c, void* stream, const uint8_t* d_
                                     int64_t* d_position_ids, int64_t* d_sequence_ids) {
   if (!c) LDDL_FAIL(-1, "null ctx");
   if (batch <= 0 || max_seq_length <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS] and [SEP]");
+  if (need_vocab(c, false)) return -1;
   if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_position_ids ||
       !d_sequence_ids || !d_dst || !d_fill || !d_seq_in_row)
     LDDL_FAIL(-1, "null output");
@@ -154,10 +139,10 @@ extern "C" int lddl_collate_seqpack(lddl_ctx* c, void* stream, const uint8_t* d_
     LDDL_FAIL(-1, "static masking needs its inputs and labels, and no special_tokens_mask");
   if (!is_static && (!d_special_tokens_mask || d_labels))
     LDDL_FAIL(-1, "null output: dynamic masking writes special_tokens_mask, and no labels");
-  SeqpackArgs E{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, d_dst, d_fill, d_seq_in_row, batch,
-                max_seq_length, d_input_ids, d_token_type_ids, d_attention_mask, d_position_ids,
-                d_sequence_ids, d_labels, d_special_tokens_mask, d_lab_bytes, d_lab_off, d_pos,
-                d_pos_off, ignore_index, 0, {}, {}};
+  SeqpackArgs E{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb}, d_dst, d_fill, d_seq_in_row,
+                batch, max_seq_length, d_input_ids, d_token_type_ids, d_attention_mask,
+                d_position_ids, d_sequence_ids, d_labels, d_special_tokens_mask,
+                {d_lab_bytes, d_lab_off, d_pos, d_pos_off}, ignore_index, 0, {}, {}};
   return launch<kPlain>(E, stream);
 }
 
@@ -174,17 +159,14 @@ extern "C" int lddl_collate_seqpack_masked(lddl_ctx* c, void* stream, const uint
                                            uint64_t counter, int32_t whole_word) {
   if (!c) LDDL_FAIL(-1, "null ctx");
   if (batch <= 0 || max_seq_length <= 0) return 0;
-  if (c->tab.special_id[kCls] < 0 || c->tab.special_id[kSep] < 0 || c->tab.special_id[kMask] < 0)
-    LDDL_FAIL(-1, "vocab needs [CLS], [SEP] and [MASK]");
+  if (need_vocab(c, true)) return -1;
   if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels || !d_position_ids ||
       !d_sequence_ids || !d_dst || !d_fill || !d_seq_in_row)
     LDDL_FAIL(-1, "null output");
-  SeqpackArgs E{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb, d_dst, d_fill, d_seq_in_row, batch,
-                max_seq_length, d_input_ids, d_token_type_ids, d_attention_mask, d_position_ids,
-                d_sequence_ids, d_labels, nullptr, nullptr, nullptr, nullptr, nullptr,
-                ignore_index, draw_stride,
-                MaskDraw{mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, seed,
-                         counter},
-                ContBits{c->d_cont_bits, c->vocab_size}};
+  SeqpackArgs E{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb}, d_dst, d_fill, d_seq_in_row,
+                batch, max_seq_length, d_input_ids, d_token_type_ids, d_attention_mask,
+                d_position_ids, d_sequence_ids, d_labels, nullptr, {}, ignore_index, draw_stride,
+                mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
+                cont_bits_of(c)};
   return whole_word ? launch<kFusedWw>(E, stream) : launch<kFused>(E, stream);
 }

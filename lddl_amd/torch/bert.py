@@ -14,6 +14,7 @@ batch through a reused pinned ring (`HostStager`), runs the encode + masking ker
 the user's extra collate_fn. The HIP Context is created only after every bin's workers have
 started (`_LazyContext`). Sample order, bin choice and epoch logic are the reference's.
 """
+import contextlib
 import logging
 import os
 
@@ -26,6 +27,7 @@ from ..utils import get_all_bin_ids, get_all_parquets_under, get_file_paths_for_
 from .dataloader import Binned, DataLoader
 from .datasets import ParquetDataset  # noqa: F401
 from .log import DatasetLogger
+from .online import _empty_long, _roundup
 from .packing import (BertPretrainDataset, PackedBatch, _canon, _decode_record_batch,  # noqa: F401
                       _npy_u16, _ntok, _pack, _pack_batch)
 from .seqpack import SeqPackedBatch, plan_rows, seqpack_collate  # noqa: F401
@@ -148,6 +150,21 @@ def _mask_tokens(inputs, special_tokens_mask=None, tokenizer=None, mlm_probabili
     return inputs, labels
 
 
+@contextlib.contextmanager
+def _timed(events):
+    """Record the pair of timing events, if there is one, around the block."""
+    if events is not None:
+        events[0].record()
+    yield
+    if events is not None:
+        events[1].record()
+
+
+def _mask_args(ctx, mask, ignore_index):
+    p, seed, counter = mask
+    return float(p), ignore_index, len(ctx), seed, counter
+
+
 def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=None, events=None,
                   stager=None, loss_mask=False, whole_word=False):
     """`_to_encoded_inputs` on an already packed batch (main process, GPU).
@@ -166,7 +183,7 @@ def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=No
     dev = ctx.device
     B = len(pk)
     seq = int((pk.na + pk.nb).max()) + 3  # the batch's shape (bert.py:91-96), known on the host
-    L = ((seq - 1) // sequence_length_alignment + 1) * sequence_length_alignment
+    L = _roundup(seq, sequence_length_alignment)
     host = [pk.blob, np.concatenate([pk.a_off, pk.b_off]), np.concatenate([pk.na, pk.nb]), pk.nsl]
     if pk.static:
         lab_off, pos, pos_off = pk.extra
@@ -178,51 +195,30 @@ def encode_packed(pk, ctx, sequence_length_alignment=8, ignore_index=-1, mask=No
     d_blob, d_off, d_cnt, d_nsl = staged[:4]
     d_a, d_b = d_off[:B + 1], d_off[B + 1:]
     d_na, d_nb = d_cnt[:B], d_cnt[B:]
-    out = {k: torch.empty(B, L, dtype=torch.long, device=dev)
-           for k in ('input_ids', 'token_type_ids', 'attention_mask')}
-    if mask is not None and not pk.static:
-        p, seed, counter = mask
-        labels = torch.empty(B, L, dtype=torch.long, device=dev)
-        if events is not None:
-            events[0].record()
-        fused = lib.lddl_collate_encode_masked_ww if whole_word else lib.lddl_collate_encode_masked
-        check(fused(
-            ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b), _ptr(d_na), _ptr(d_nb), B,
-            L, _ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']),
-            _ptr(labels), float(p), ignore_index, len(ctx), seed, counter))
-        if events is not None:
-            events[1].record()
-        out['next_sentence_labels'] = d_nsl
-        out['labels'] = labels
-        return out
-    stm = labels = d_lab_off = d_pos = d_pos_off = None
-    if pk.static:
-        d_lab_off, d_pos_off, d_pos = staged[4:]
-        labels = torch.empty(B, L, dtype=torch.long, device=dev)
-    else:
-        stm = torch.empty(B, L, dtype=torch.long, device=dev)
-    args = (ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b), _ptr(d_na), _ptr(d_nb), B, L,
-            _ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']),
-            _ptr(stm), _ptr(d_blob) if pk.static else None, _ptr(d_lab_off), _ptr(d_pos),
-            _ptr(d_pos_off), _ptr(labels), ignore_index)
-    lm = None
-    if loss_mask and pk.static:
-        lm = torch.empty(B, L, dtype=torch.long, device=dev)
-    if events is not None:
-        events[0].record()
-    if lm is not None:
-        check(lib.lddl_collate_encode_mp(*args, _ptr(lm)))
-    else:
-        check(lib.lddl_collate_encode(*args))
-    if events is not None:
-        events[1].record()
+    fused = mask is not None and not pk.static
+    out = _empty_long(dev, (B, L), ('input_ids', 'token_type_ids', 'attention_mask'))
     out['next_sentence_labels'] = d_nsl
-    if pk.static:
-        out['labels'] = labels
-        if lm is not None:
-            out['masked_lm_positions'] = lm
-    else:
-        out['special_tokens_mask'] = stm
+    out.update(_empty_long(dev, (B, L), (
+        'labels' if fused or pk.static else 'special_tokens_mask',)))
+    head = lambda: (  # noqa: E731  the arguments every entry point leads with
+        ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b), _ptr(d_na), _ptr(d_nb), B, L,
+        _ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']))
+    if fused:
+        fn = lib.lddl_collate_encode_masked_ww if whole_word else lib.lddl_collate_encode_masked
+        with _timed(events):
+            check(fn(*head(), _ptr(out['labels']), *_mask_args(ctx, mask, ignore_index)))
+        return out
+    d_lab_off, d_pos_off, d_pos = staged[4:] if pk.static else (None, None, None)
+    args = head() + (_ptr(out.get('special_tokens_mask')), _ptr(d_blob) if pk.static else None,
+                     _ptr(d_lab_off), _ptr(d_pos), _ptr(d_pos_off), _ptr(out.get('labels')),
+                     ignore_index)
+    if loss_mask and pk.static:
+        out.update(_empty_long(dev, (B, L), ('masked_lm_positions',)))
+    with _timed(events):
+        if loss_mask and pk.static:
+            check(lib.lddl_collate_encode_mp(*args, _ptr(out['masked_lm_positions'])))
+        else:
+            check(lib.lddl_collate_encode(*args))
     return out
 
 
@@ -253,7 +249,7 @@ def encode_seqpacked(spk, ctx, max_seq_length, sequence_length_alignment=8, igno
         raise ValueError('the batch was planned for rows of {} slots, not {}'.format(
             plan.capacity, L))
     lens = (spk.na + spk.nb + 3).astype(np.int32)
-    stride = ((int(lens.max()) - 1) // sequence_length_alignment + 1) * sequence_length_alignment
+    stride = _roundup(lens.max(), sequence_length_alignment)
     order, R = plan.order, plan.R
     dst = plan.row.astype(np.int64) * L + plan.start
     host = [spk.blob,
@@ -272,33 +268,25 @@ def encode_seqpacked(spk, ctx, max_seq_length, sequence_length_alignment=8, igno
     d_blob, d_i64, d_i32 = staged[:3]
     d_a, d_b, d_dst = d_i64[:B + 1], d_i64[B + 1:2 * B + 2], d_i64[2 * B + 2:3 * B + 2]
     d_na, d_nb, d_fill, d_seq = (d_i32[k * B:(k + 1) * B] for k in range(4))
-    names = ('input_ids', 'token_type_ids', 'attention_mask', 'position_ids', 'sequence_ids')
     fused = mask is not None and not spk.static
-    names += ('labels',) if fused or spk.static else ('special_tokens_mask',)
-    out = {k: torch.empty(R, L, dtype=torch.long, device=dev) for k in names}
+    out = _empty_long(dev, (R, L), ('input_ids', 'token_type_ids', 'attention_mask',
+                                    'position_ids', 'sequence_ids',
+                                    'labels' if fused or spk.static else 'special_tokens_mask'))
     head = (ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b), _ptr(d_na), _ptr(d_nb), B,
             _ptr(d_dst), _ptr(d_fill), _ptr(d_seq), L)
-    if events is not None:
-        events[0].record()
-    if fused:
-        p, seed, counter = mask
-        check(lib.lddl_collate_seqpack_masked(
-            *head, stride, _ptr(out['input_ids']), _ptr(out['token_type_ids']),
-            _ptr(out['attention_mask']), _ptr(out['labels']), _ptr(out['position_ids']),
-            _ptr(out['sequence_ids']), float(p), ignore_index, len(ctx), seed, counter,
-            1 if whole_word else 0))
-    else:
-        d_lab_off = d_pos_off = d_pos = None
-        if spk.static:
-            d_lab_off, d_pos_off, d_pos = staged[3:]
-        check(lib.lddl_collate_seqpack(
-            *head, _ptr(out['input_ids']), _ptr(out['token_type_ids']),
-            _ptr(out['attention_mask']), _ptr(out.get('special_tokens_mask')),
-            _ptr(d_blob) if spk.static else None, _ptr(d_lab_off), _ptr(d_pos), _ptr(d_pos_off),
-            _ptr(out.get('labels')), ignore_index, _ptr(out['position_ids']),
-            _ptr(out['sequence_ids'])))
-    if events is not None:
-        events[1].record()
+    with _timed(events):
+        outs = (_ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']))
+        tail = (_ptr(out['position_ids']), _ptr(out['sequence_ids']))
+        if fused:
+            check(lib.lddl_collate_seqpack_masked(
+                *head, stride, *outs, _ptr(out['labels']), *tail,
+                *_mask_args(ctx, mask, ignore_index), 1 if whole_word else 0))
+        else:
+            d_lab_off, d_pos_off, d_pos = staged[3:] if spk.static else (None, None, None)
+            check(lib.lddl_collate_seqpack(
+                *head, *outs, _ptr(out.get('special_tokens_mask')),
+                _ptr(d_blob) if spk.static else None, _ptr(d_lab_off), _ptr(d_pos),
+                _ptr(d_pos_off), _ptr(out.get('labels')), ignore_index, *tail))
     out['next_sentence_labels'] = d_i64[3 * B + 2:4 * B + 2]
     out['cls_positions'] = d_i64[4 * B + 2:]
     out['seq_lens'] = d_i32[4 * B:]

@@ -156,6 +156,69 @@ def _roundup(n, a):
     return ((int(n) - 1) // a + 1) * a
 
 
+def _table_static(ctx, pb):
+    """Whether the pair table carries static masking; its id width must be the context's."""
+    static = pb.pos is not None
+    if pb.tokens.element_size() != ctx.id_bytes or (
+            static and pb.labels.element_size() != ctx.id_bytes):
+        raise ValueError('pair table ids are {}-byte, the context collates {}-byte ids'.format(
+            pb.tokens.element_size(), ctx.id_bytes))
+    return static
+
+
+def _row_stats(pb, rows, more=(), per_sample=False):
+    """The host checks' one sync: [rows.min(), rows.max(), longest row, *more] and, with static
+    positions, the rows' largest position (per_sample: the largest position - its own sample's
+    length, then that position). IndexError for a row outside the table; the rest is the
+    caller's."""
+    import torch
+    n, ntok, dev = pb.n_pairs, pb.num_tokens, pb.num_tokens.device
+    if rows is None:
+        stat = [ntok.new_zeros(()), ntok.new_full((), n - 1), ntok.max()]
+    else:
+        stat = [rows.min(), rows.max(), ntok[rows.clamp(0, n - 1)].max()]
+    stat += more
+    if pb.pos is not None and pb.pos.numel():
+        sel = torch.ones(n, dtype=torch.bool, device=dev)
+        if rows is not None:
+            sel = torch.zeros(n, dtype=torch.bool, device=dev)
+            sel[rows.clamp(0, n - 1)] = True
+        seg = torch.repeat_interleave(torch.arange(n, device=dev),
+                                      pb.pos_off[1:] - pb.pos_off[:-1],
+                                      output_size=pb.pos.numel())
+        p = pb.pos.to(torch.int64) & 0xFFFF  # uint16 positions in int16 storage
+        if per_sample:
+            over = torch.where(sel[seg], p - ntok[seg], torch.full_like(p, -1))
+            stat += [over.max(), p[over.argmax()]]
+        else:
+            stat.append(torch.where(sel[seg], p, torch.zeros_like(p)).max())
+    stat = torch.stack(stat).tolist()  # the one sync
+    if stat[0] < 0 or stat[1] >= n:
+        raise IndexError('rows hold {}..{}, the table has {} pairs'.format(stat[0], stat[1], n))
+    return stat
+
+
+def _table_args(ctx, pb, static):
+    """(ctx, stream, table), (pos, labels, pos_off): what a lddl_collate_pairs* call leads with."""
+    from ..context import _ptr, _stream
+    head = (ctx.handle, _stream(), _ptr(pb.tokens), _ptr(pb.tok_off), _ptr(pb.len_a),
+            _ptr(pb.is_random_next))
+    st = (_ptr(pb.pos), _ptr(pb.labels), _ptr(pb.pos_off)) if static else (None, None, None)
+    return head, st
+
+
+def _mask_args(ctx, mask, ignore_index, whole_word):
+    """The trailing arguments of the two *_masked entry points."""
+    p, seed, counter = mask
+    return (float(p), ignore_index, len(ctx), int(seed) & _M64, int(counter) & _M64,
+            1 if whole_word else 0)
+
+
+def _empty_long(dev, shape, names):
+    import torch
+    return {key: torch.empty(*shape, dtype=torch.long, device=dev) for key in names}
+
+
 def collate_pairs(ctx, pb, rows=None, sequence_length_alignment=8, ignore_index=-1, mask=None,
                   whole_word=False, seq_len=None, *, check=True):
     """`encode_packed` for rows `rows` (int64 cuda tensor of pair indices, None = all, in order)
@@ -172,36 +235,15 @@ def collate_pairs(ctx, pb, rows=None, sequence_length_alignment=8, ignore_index=
     widths come from the table itself, passes seq_len and check=False and never waits."""
     import torch
     from .._native import check as _check, lib
-    from ..context import _ptr, _stream
+    from ..context import _ptr
     dev = ctx.device
-    static = pb.pos is not None
-    if pb.tokens.element_size() != ctx.id_bytes or (
-            static and pb.labels.element_size() != ctx.id_bytes):
-        raise ValueError('pair table ids are {}-byte, the context collates {}-byte ids'.format(
-            pb.tokens.element_size(), ctx.id_bytes))
+    static = _table_static(ctx, pb)
     n = pb.n_pairs
     if rows is not None:
         assert rows.dtype == torch.int64 and rows.is_cuda and rows.is_contiguous()
     B = n if rows is None else rows.numel()
     if B and (seq_len is None or check):
-        ntok = pb.num_tokens
-        if rows is None:
-            stat = [ntok.new_zeros(()), ntok.new_full((), n - 1), ntok.max()]
-        else:
-            stat = [rows.min(), rows.max(), ntok[rows.clamp(0, n - 1)].max()]
-        if static and pb.pos.numel():
-            sel = torch.ones(n, dtype=torch.bool, device=dev)
-            if rows is not None:
-                sel = torch.zeros(n, dtype=torch.bool, device=dev)
-                sel[rows.clamp(0, n - 1)] = True
-            seg = torch.repeat_interleave(torch.arange(n, device=dev),
-                                          pb.pos_off[1:] - pb.pos_off[:-1],
-                                          output_size=pb.pos.numel())
-            p = pb.pos.to(torch.int64) & 0xFFFF  # uint16 positions in int16 storage
-            stat.append(torch.where(sel[seg], p, torch.zeros_like(p)).max())
-        stat = torch.stack(stat).tolist()  # the one sync
-        if stat[0] < 0 or stat[1] >= n:
-            raise IndexError('rows hold {}..{}, the table has {} pairs'.format(stat[0], stat[1], n))
+        stat = _row_stats(pb, rows)
         if seq_len is None:
             seq_len = _roundup(stat[2], sequence_length_alignment)
         if stat[2] > seq_len:
@@ -211,25 +253,19 @@ def collate_pairs(ctx, pb, rows=None, sequence_length_alignment=8, ignore_index=
             raise IndexError('masked_lm_positions holds {} >= sequence length {}'.format(
                 stat[3], seq_len))
     L = int(seq_len or 0)
-    out = {k: torch.empty(B, L, dtype=torch.long, device=dev)
-           for k in ('input_ids', 'token_type_ids', 'attention_mask')}
+    fused = mask is not None and not static
+    out = _empty_long(dev, (B, L), ('input_ids', 'token_type_ids', 'attention_mask'))
     nsl = out['next_sentence_labels'] = torch.empty(B, dtype=torch.long, device=dev)
-    head = (ctx.handle, _stream(), _ptr(pb.tokens), _ptr(pb.tok_off), _ptr(pb.len_a),
-            _ptr(pb.is_random_next))
+    out.update(_empty_long(dev, (B, L), ('labels' if fused or static else 'special_tokens_mask',)))
+    head, st = _table_args(ctx, pb, static)
     outs = (_ptr(out['input_ids']), _ptr(out['token_type_ids']), _ptr(out['attention_mask']))
-    if mask is not None and not static:
-        p, seed, counter = mask
-        labels = out['labels'] = torch.empty(B, L, dtype=torch.long, device=dev)
-        _check(lib.lddl_collate_pairs_masked(*head, _ptr(rows), B, L, *outs, _ptr(labels),
-                                             _ptr(nsl), float(p), ignore_index, len(ctx),
-                                             int(seed) & _M64, int(counter) & _M64,
-                                             1 if whole_word else 0))
+    if fused:
+        _check(lib.lddl_collate_pairs_masked(*head, _ptr(rows), B, L, *outs, _ptr(out['labels']),
+                                             _ptr(nsl),
+                                             *_mask_args(ctx, mask, ignore_index, whole_word)))
         return out
-    key = 'labels' if static else 'special_tokens_mask'
-    t = out[key] = torch.empty(B, L, dtype=torch.long, device=dev)
-    st = (_ptr(pb.pos), _ptr(pb.labels), _ptr(pb.pos_off)) if static else (None, None, None)
     _check(lib.lddl_collate_pairs(*head, *st, _ptr(rows), B, L, *outs,
-                                  None if static else _ptr(t), _ptr(t) if static else None,
+                                  _ptr(out.get('special_tokens_mask')), _ptr(out.get('labels')),
                                   _ptr(nsl), ignore_index))
     return out
 
@@ -327,13 +363,9 @@ def collate_pairs_seqpacked(ctx, pb, rows, plan, k, R, max_seq_length, draw_stri
     import ctypes
     import torch
     from .._native import check as _check, lib
-    from ..context import _ptr, _stream
+    from ..context import _ptr
     dev = ctx.device
-    static = pb.pos is not None
-    if pb.tokens.element_size() != ctx.id_bytes or (
-            static and pb.labels.element_size() != ctx.id_bytes):
-        raise ValueError('pair table ids are {}-byte, the context collates {}-byte ids'.format(
-            pb.tokens.element_size(), ctx.id_bytes))
+    static = _table_static(ctx, pb)
     L = int(max_seq_length)
     if plan.capacity != L:
         raise ValueError('the batch was planned for rows of {} slots, not {}'.format(
@@ -347,26 +379,7 @@ def collate_pairs_seqpacked(ctx, pb, rows, plan, k, R, max_seq_length, draw_stri
     elif (b0, b1) != (0, n):
         rows = torch.arange(b0, b1, device=dev)
     if B and (check or R is None):
-        ntok = pb.num_tokens
-        if rows is None:
-            stat = [ntok.new_zeros(()), ntok.new_full((), n - 1), ntok.max()]
-        else:
-            stat = [rows.min(), rows.max(), ntok[rows.clamp(0, n - 1)].max()]
-        stat.append(plan.num_rows[k].to(ntok.dtype))
-        if static and pb.pos.numel():
-            sel = torch.ones(n, dtype=torch.bool, device=dev)
-            if rows is not None:
-                sel = torch.zeros(n, dtype=torch.bool, device=dev)
-                sel[rows.clamp(0, n - 1)] = True
-            seg = torch.repeat_interleave(torch.arange(n, device=dev),
-                                          pb.pos_off[1:] - pb.pos_off[:-1],
-                                          output_size=pb.pos.numel())
-            p = pb.pos.to(torch.int64) & 0xFFFF  # uint16 positions in int16 storage
-            over = torch.where(sel[seg], p - ntok[seg], torch.full_like(p, -1))
-            stat += [over.max(), p[over.argmax()]]
-        stat = torch.stack(stat).tolist()  # the one sync
-        if stat[0] < 0 or stat[1] >= n:
-            raise IndexError('rows hold {}..{}, the table has {} pairs'.format(stat[0], stat[1], n))
+        stat = _row_stats(pb, rows, [plan.num_rows[k].to(pb.num_tokens.dtype)], per_sample=True)
         if stat[2] > L:
             raise ValueError('a pair of {} tokens does not fit the sequence length {}'.format(
                 stat[2], L))
@@ -378,15 +391,14 @@ def collate_pairs_seqpacked(ctx, pb, rows, plan, k, R, max_seq_length, draw_stri
         elif R != stat[3]:
             raise ValueError('R = {}, the plan of batch {} has {} rows'.format(R, k, stat[3]))
     R = int(R or 0) if B else 0
-    names = ('input_ids', 'token_type_ids', 'attention_mask', 'position_ids', 'sequence_ids')
     fused = mask is not None and not static
-    names += ('labels',) if fused or static else ('special_tokens_mask',)
-    out = {key: torch.empty(R, L, dtype=torch.long, device=dev) for key in names}
+    out = _empty_long(dev, (R, L), ('input_ids', 'token_type_ids', 'attention_mask',
+                                    'position_ids', 'sequence_ids',
+                                    'labels' if fused or static else 'special_tokens_mask'))
     nsl = out['next_sentence_labels'] = torch.empty(B, dtype=torch.long, device=dev)
     cls = out['cls_positions'] = torch.empty(B, dtype=torch.long, device=dev)
     lens = out['seq_lens'] = torch.empty(B, dtype=torch.int32, device=dev)
-    head = (ctx.handle, _stream(), _ptr(pb.tokens), _ptr(pb.tok_off), _ptr(pb.len_a),
-            _ptr(pb.is_random_next))
+    head, st = _table_args(ctx, pb, static)
     at = lambda t: ctypes.c_void_p(t.data_ptr() + b0 * t.element_size())  # noqa: E731  &t[b0]
     body = (_ptr(rows), B, at(plan.dst), at(plan.fill), at(plan.seq_in_row),
             at(plan.packed_idx), R, L)
@@ -394,13 +406,10 @@ def collate_pairs_seqpacked(ctx, pb, rows, plan, k, R, max_seq_length, draw_stri
     tail = (_ptr(out['position_ids']), _ptr(out['sequence_ids']), _ptr(nsl), _ptr(cls),
             _ptr(lens))
     if fused:
-        p, seed, counter = mask
         _check(lib.lddl_collate_pairs_seqpack_masked(
-            *head, *body, int(draw_stride), *outs, _ptr(out['labels']), *tail, float(p),
-            ignore_index, len(ctx), int(seed) & _M64, int(counter) & _M64,
-            1 if whole_word else 0))
+            *head, *body, int(draw_stride), *outs, _ptr(out['labels']), *tail,
+            *_mask_args(ctx, mask, ignore_index, whole_word)))
         return out
-    st = (_ptr(pb.pos), _ptr(pb.labels), _ptr(pb.pos_off)) if static else (None, None, None)
     _check(lib.lddl_collate_pairs_seqpack(
         *head, *st, *body, *outs, _ptr(out.get('special_tokens_mask')), _ptr(out.get('labels')),
         *tail, ignore_index))

@@ -216,6 +216,28 @@ def test_whole_word_differs_from_plain_where_words_have_pieces(ctx, tables):
         assert torch.equal(a[k], b[k])
 
 
+def test_hand_made_window_edges_equal_the_string_path(ctx):
+    """test_online_seqpack_gpu.edge_samples (a [SEP] on slot 63 and on slot 64, '##' pieces that
+    begin A and B, the smallest pair) as a table of its own against the string path, in every
+    mode. The ids are ASCII words and pieces: each string is one vocab line, so the rendered
+    sample splits and looks up to the ids it came from."""
+    from test_online_seqpack_gpu import _pair_batch, _with_static, edge_samples
+    toks = ctx.tokens
+    words = np.array([i for i in range(1000, 6000) if toks[i].isascii() and toks[i].isalpha()])
+    cont = np.array([i for i, t in enumerate(toks)
+                     if t.startswith('##') and t.isascii() and t[2:].isalnum()][:500])
+    assert len(words) > 1000 and len(cont) == 500
+    rng = np.random.default_rng(11)
+    samples, _ = edge_samples(rng, words, cont)
+    pb = _pair_batch(ctx, samples)
+    assert _check_plain(ctx, pb, None)['input_ids'].shape == (5, 72)
+    for ww in (False, True):
+        _check_masked(ctx, pb, None, 0.5, ww)
+    at = [[1, 62, 64, 68], [1, 63, 65], [1, 62], [63], [1, 3]]
+    _check_plain(ctx, _pair_batch(ctx, [_with_static(rng, words, s, p)
+                                        for s, p in zip(samples, at)]), None)
+
+
 def test_four_byte_ids(tmp_path):
     """A vocab of more than 65,534 lines: 4-byte ids in the table (lddl_ctx_id_bytes)."""
     from lddl_amd import synth

@@ -130,6 +130,54 @@ def test_lengths_around_half_a_row(ctx, ids, mode):
     assert plan.start.tolist() == [0, 0, 0, 64, 0, 0]
 
 
+def edge_samples(rng, words, cont):
+    """Five samples of at most 70 slots that put the layout's edges on the edge of a 64-slot
+    window, and the (sample, slot) of every '##' piece that is the first token of its A or B:
+      0  na = 62: the first [SEP] on slot 63, B begins on slot 64; 70 slots
+      1  na = 63: the first [SEP] on slot 64; 70 slots
+      2  64 slots: the last [SEP] on slot 63
+      3  65 slots: the last [SEP] on slot 64
+      4  na = nb = 1: the smallest pair, 5 slots
+    A and B of 0, 1 and 4 and A of 2 begin with a '##' piece. Directly behind [CLS] / [SEP] it
+    continues nothing: it is a word head. The one behind it is a word of its own."""
+    w = lambda k: words[rng.integers(0, len(words), k)]  # noqa: E731
+    c = lambda: cont[rng.integers(0, len(cont), 1)]  # noqa: E731
+    samples = [[np.concatenate([c(), w(61)]), np.concatenate([c(), w(4)]), True],
+               [np.concatenate([c(), w(62)]), np.concatenate([c(), w(3)]), False],
+               [np.concatenate([c(), w(29)]), w(31), False],
+               [w(40), w(22), True],
+               [c(), c(), False]]
+    heads = [(0, 1), (0, 64), (1, 1), (1, 65), (2, 1), (4, 1), (4, 3)]
+    return samples, heads
+
+
+@pytest.mark.parametrize('mode', MODES)
+def test_separators_and_pieces_on_the_window_edge(ctx, ids, mode):
+    """edge_samples (B = 5: a partly filled block) into rows of 128, unpacked against packed."""
+    rng = np.random.default_rng(11)
+    words, cont = ids
+    samples, heads = edge_samples(rng, words, cont)
+    assert [len(s[0]) + len(s[1]) + 3 for s in samples] == [70, 70, 64, 65, 5]
+    assert [len(s[0]) for s in samples[:2]] == [62, 63]
+    if mode == 'static':  # labels on the slots beside and on the separators' neighbours
+        at = [[1, 62, 64, 68], [1, 63, 65], [1, 62], [63], [1, 3]]
+        samples = [_with_static(rng, words, s, p) for s, p in zip(samples, at)]
+    pb, rows = _scatter(rng, ctx, words, samples, mode == 'static')
+    both(ctx, pb, rows, 128, mode)
+    if mode != 'whole_word':
+        return
+    # a head's decision is its own draw: on these slots whole-word equals per-token masking
+    seen = set()
+    for counter in range(COUNTER, COUNTER + 4):
+        m = (0.5, SEED, counter)
+        ww = both(ctx, pb, rows, 128, 'whole_word', m)[2]['labels'].cpu().numpy()
+        tok = both(ctx, pb, rows, 128, 'fused', m)[2]['labels'].cpu().numpy()
+        for i, x in heads:
+            assert ww[i, x] == tok[i, x], (counter, i, x)
+            seen.add(bool(ww[i, x] != IGN))
+    assert seen == {True, False}
+
+
 def test_identity_rows_and_unaligned_capacity(ctx, ids):
     """rows=None over a table of its own, and a capacity that is no multiple of 8 or 64."""
     rng = np.random.default_rng(8)
