@@ -145,7 +145,8 @@ int lddl_utf8_check(void* stream, const uint8_t* d_text, int64_t n_bytes, int64_
  * Replaces `nltk.tokenize.sent_tokenize(text)` + `strip()` + dropping empty sentences
  * (lddl/dask/bert/pretrain.py:86-88) for every document of a batch: nltk 3.6.5's
  * PunktSentenceTokenizer(params).span_tokenize (nltk/tokenize/punkt.py:1316-1391, realign
- * 1351-1379, annotation 582-630 / 1516-1650), segment.hip.
+ * 1351-1379, annotation 582-630 / 1516-1650): kernels in segment.hip, annotation in punkt_dev.h,
+ * the tables of lddl_punkt_set_params in punkt.hip (parsed on the host by punkt_params.h).
  * lddl_punkt_set_params: `table` = lddl_amd/assets/punkt_props.bin (Python's character classes),
  *   `records` = the PunktParameters (abbrev_types, sent_starters, ortho_context, collocations)
  *   as records (u8 kind 1/2/3/4, u8 value = ortho flags, u16 len_a, u16 len_b, UTF-8 bytes a, b);

@@ -1,6 +1,7 @@
 """BART pretraining chunks on the GPU: the reference's `_aggregate_sentences`
 (lddl/dask/bart/pretrain.py:88-128) for a whole batch of segmented documents at once
-(csrc/bart.hip, C-ABI `lddl_bart_count` / `lddl_bart_fill`).
+(csrc/bart.hip, C-ABI `lddl_bart_count` / `lddl_bart_fill`; whitespace is the class table of
+csrc/punkt.hip read through csrc/punkt_classes.h).
 
 Per document, sentences in order: `chunk += " " + sentence`, `num_tokens +=
 len(sentence.split())`; the chunk is emitted and both reset when `num_tokens >=

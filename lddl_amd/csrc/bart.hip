@@ -39,6 +39,7 @@
 #include "ctx.h"
 #include "device.h"
 #include "lddl_amd.h"
+#include "punkt_classes.h"
 #include "scan.h"
 
 namespace lddl {
@@ -49,20 +50,9 @@ constexpr int kTileThreads = 256;
 constexpr int kPer = kTile / (16 * kTileThreads);  // 16-byte pieces per thread, kTileThreads apart
 constexpr int kPad = 16;         // bytes staged on either side of a text tile (4 are needed)
 
-struct ClassTab {
-  const uint16_t* l1;
-  const uint8_t* pages;
-};
-
-// Python str.isspace() on ASCII: \t \n \v \f \r, \x1c-\x1f, space
-__device__ __forceinline__ bool ascii_space(uint32_t c) {
-  return c < 64 && ((0x00000001F0003E00ull >> c) & 1ull);
-}
-
-// class bit 0 (str.isspace()) of a code point >= 0x80
+// str.isspace() of a code point >= 0x80
 __device__ __forceinline__ bool table_space(const ClassTab& t, uint32_t v) {
-  if (v >= 0x110000u) return false;
-  return (t.pages[(uint32_t)t.l1[v >> 8] * 256u + (v & 255u)] & 1u) != 0;
+  return (class_bits(t, v) & kPSpace) != 0;
 }
 
 // Only code points whose UTF-8 form starts with C2, E1, E2 or E3 are whitespace (U+0085 ...
@@ -440,10 +430,8 @@ struct lddl_bart_state {
   std::unique_ptr<PendingBart> pending;
 };
 
-static lddl_bart_state* bart_of(lddl_ctx* c) { return reinterpret_cast<lddl_bart_state*>(c->bart); }
-
 extern "C" void lddl_bart_release(lddl_ctx* c) {
-  delete bart_of(c);  // (a pending aggregation's blocks go back to the arena)
+  delete c->bart;  // (a pending aggregation's blocks go back to the arena)
   c->bart = nullptr;
 }
 
@@ -452,13 +440,13 @@ extern "C" int lddl_bart_count(lddl_ctx* c, void* stream, const uint8_t* d_text,
                                int64_t n_doc, int32_t target_words, int64_t* n_chunks, int64_t* n_out_bytes) {
   if (!c) LDDL_FAIL(-1, "null ctx");
   ClassTab t{};
-  if (!lddl_punkt_tables(c, &t.l1, &t.pages))
+  if (!punkt_class_tab(c, &t))
     LDDL_FAIL(-1, "Punkt parameters not set (lddl_punkt_set_params): lddl_bart_count needs the character classes");
   if (n_bytes < 0 || n_sent < 0 || n_doc < 0 || !n_chunks || !n_out_bytes || !d_sent_off || !d_doc_sent_off)
     LDDL_FAIL(-1, "bad sizes");
   if (n_doc == 0 && n_sent != 0) LDDL_FAIL(-1, "sentences without documents");
   if (!c->bart) c->bart = new lddl_bart_state();
-  lddl_bart_state* bs = bart_of(c);
+  lddl_bart_state* bs = c->bart;
   if (bs->pending) LDDL_FAIL(-1, "an aggregation is pending: call lddl_bart_fill first");
   hipStream_t st = as_stream(stream);
   // local until the count is complete: an error return gives the blocks back
@@ -507,7 +495,7 @@ extern "C" int lddl_bart_count(lddl_ctx* c, void* stream, const uint8_t* d_text,
 extern "C" int lddl_bart_fill(lddl_ctx* c, void* stream, uint8_t* d_out, int64_t* d_chunk_off,
                               int32_t* d_num_tokens, int64_t* d_doc_chunk_off) {
   if (!c) LDDL_FAIL(-1, "null ctx");
-  lddl_bart_state* bs = bart_of(c);
+  lddl_bart_state* bs = c->bart;
   if (!bs || !bs->pending) LDDL_FAIL(-1, "no pending aggregation (lddl_bart_count)");
   hipStream_t st = as_stream(stream);
   // the call ends the pending aggregation, whatever it returns (all outputs null: cancel)

@@ -8,6 +8,8 @@
 
 #include "arena.h"
 #include "device.h"
+struct lddl_punkt_state;  // punkt_state.h
+struct lddl_bart_state;   // bart.hip
 struct lddl_ctx {
   int device = 0;
   lddl::Tables tab{};
@@ -33,17 +35,26 @@ struct lddl_ctx {
   size_t lds_per_block = 0;         // hipDeviceAttributeMaxSharedMemoryPerBlock of `device`
   std::vector<std::string> tokens;  // host copy of the vocab lines
   lddl::DevArena arena;             // per-call temporaries (pair plans)
-  void* punkt = nullptr;            // lddl_punkt_state (segment.hip), created by lddl_punkt_set_params
-  void* bart = nullptr;             // lddl_bart_state (bart.hip), created by lddl_bart_count
+  lddl_punkt_state* punkt = nullptr;  // created by lddl_punkt_set_params (punkt.hip)
+  lddl_bart_state* bart = nullptr;    // created by lddl_bart_count (bart.hip)
   // the pair planner's side stream (pairs.hip: the tail range of a split plan), created on first
   // use: non-blocking, lowest priority
   hipStream_t plan_side = nullptr;
 };
 extern "C" void lddl_punkt_release(lddl_ctx* c);
 extern "C" void lddl_bart_release(lddl_ctx* c);
-// the character class table of lddl_punkt_set_params (bit 0 = str.isspace()); 0 if it was never set
-extern "C" int lddl_punkt_tables(lddl_ctx* c, const uint16_t** l1, const uint8_t** pages);
 
 namespace lddl {
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+// device copy of a host array (at least 16 bytes, so never null); *dst owns it, also when the
+// copy fails
+template <typename T>
+int upload(T** dst, const void* src, size_t bytes) {
+  LDDL_HIP(hipMalloc((void**)dst, bytes ? bytes : 16));
+  if (bytes) LDDL_HIP(hipMemcpy((void*)*dst, src, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+// the character class table of lddl_punkt_set_params (punkt_classes.h); false if it was never set
+struct ClassTab;
+bool punkt_class_tab(const lddl_ctx* c, ClassTab* out);
 }  // namespace lddl

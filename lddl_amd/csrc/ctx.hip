@@ -10,13 +10,6 @@ using namespace lddl;
 
 namespace {
 
-template <typename T>
-int upload(T** dst, const void* src, size_t bytes) {
-  LDDL_HIP(hipMalloc((void**)dst, bytes ? bytes : 16));
-  if (bytes) LDDL_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-
 uint64_t pack8(const uint8_t* p, int len) {
   uint64_t v = 0;
   for (int i = 0; i < len && i < 8; ++i) v |= (uint64_t)p[i] << (8 * i);

@@ -1,6 +1,6 @@
 """Host sentence segmentation (`--sentence-splitter host`): the reference's own
 `nltk.tokenize.sent_tokenize` (lddl/dask/bert/pretrain.py:86, 583), for debugging and A/B runs
-against the GPU Punkt (lddl_amd/punkt.py + csrc/segment.hip, the default).
+against the GPU Punkt (lddl_amd/punkt.py + csrc/segment.hip and csrc/punkt.hip, the default).
 
 The reference needs nltk and downloads its English Punkt model at run time
 (`nltk.download('punkt')`). Here, with nltk importable:

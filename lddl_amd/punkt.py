@@ -1,6 +1,7 @@
 """GPU Punkt sentence segmentation: the reference's `nltk.tokenize.sent_tokenize(text)` followed by
 `strip()` and dropping empty sentences (lddl/dask/bert/pretrain.py:86-88), for a whole batch of
-documents at once (csrc/segment.hip, C-ABI `lddl_segment_count` / `lddl_segment_fill`).
+documents at once (csrc/segment.hip, C-ABI `lddl_segment_count` / `lddl_segment_fill`; the
+parameter tables are csrc/punkt.hip, `lddl_punkt_set_params`, parsed by csrc/punkt_params.h).
 
 Parameters mirror nltk's `PunktParameters` (nltk/tokenize/punkt.py:333-369, nltk 3.6.5):
 abbreviation types, collocations, frequent sentence starters and orthographic context. nltk's

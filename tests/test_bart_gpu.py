@@ -1,7 +1,7 @@
-"""BART chunk aggregation on the GPU (csrc/bart.hip through lddl_bart_count / lddl_bart_fill,
-lddl_amd/bart.py) and the `preprocess_bart_pretrain` command against the reference's output
-(tests/golden/bart.json, made by tests/golden/make_bart_golden.py from the reference's own
-`_get_sequences` and `save`)."""
+"""BART chunk aggregation on the GPU (csrc/bart.hip through lddl_bart_count / lddl_bart_fill over
+the class table of csrc/punkt.hip, lddl_amd/bart.py) and the `preprocess_bart_pretrain` command
+against the reference's output (tests/golden/bart.json, made by tests/golden/make_bart_golden.py
+from the reference's own `_get_sequences` and `save`)."""
 import json
 import os
 import random
@@ -335,3 +335,77 @@ def test_cli_invalid_utf8(tmp_path):
                                               '--punkt-params', str(tmp_path / 'punkt.json')])
     with pytest.raises(UnicodeDecodeError):
         pretrain.main(args)
+
+
+# ---- the context's state: unset tables, a pending aggregation, a closed context --------------
+
+def small_layout():
+    """Two documents of three short sentences, as lddl_segment_fill lays them out."""
+    import torch
+    docs = [['One two. ', 'Three four five. ', 'Six. '], ['Seven eight nine. ', 'Ten. ', 'Eleven twelve.']]
+    text, so, dso = layout(docs)
+    return docs, tuple(torch.from_numpy(x.copy()).cuda() for x in (text, so, dso))
+
+
+def raw_bart_count(c, t, s, d, target_words):
+    import ctypes
+    from lddl_amd._native import lib
+    from lddl_amd.context import _ptr, _stream
+    n_chunks, n_out = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    rc = lib.lddl_bart_count(c._h, _stream(), _ptr(t), t.numel(), _ptr(s), s.numel() - 1, _ptr(d),
+                             d.numel() - 1, target_words, ctypes.byref(n_chunks), ctypes.byref(n_out))
+    return rc, n_chunks.value, n_out.value
+
+
+def small_chunks(out, co, nt, dco):
+    from lddl_amd import bart
+    chunks = bart.chunk_strings(out.cpu().numpy(), co.cpu().numpy())
+    dco, nt = dco.cpu().numpy(), nt.cpu().numpy().tolist()
+    return [list(zip(chunks[dco[k]:dco[k + 1]], nt[dco[k]:dco[k + 1]])) for k in range(len(dco) - 1)]
+
+
+def test_count_needs_set_params_then_works():
+    from lddl_amd import bart, punkt
+    from lddl_amd._native import lib
+    from lddl_amd.context import Context
+    docs, (t, s, d) = small_layout()
+    c = Context(VOCAB_UNCASED, True)  # lddl_punkt_set_params never called
+    rc, _, _ = raw_bart_count(c, t, s, d, 4)
+    assert rc == -1
+    assert lib.lddl_last_error().decode() == ('Punkt parameters not set (lddl_punkt_set_params): '
+                                              'lddl_bart_count needs the character classes')
+    punkt.set_params(c, None)
+    assert small_chunks(*bart.aggregate(c, t, s, d, 7)) == ref_aggregate(docs, 7)
+    c.close()
+
+
+def test_second_count_is_refused_and_the_fill_returns_the_first(ctx):
+    import torch
+    from lddl_amd._native import check, lib
+    from lddl_amd.context import _ptr, _stream
+    docs, (t, s, d) = small_layout()
+    rc, n_chunks, n_out = raw_bart_count(ctx, t, s, d, 4)  # target_seq_length 7
+    assert rc == 0
+    rc2, _, _ = raw_bart_count(ctx, t, s, d, 1)  # (one chunk per sentence, were it counted)
+    assert rc2 == -1
+    assert lib.lddl_last_error().decode() == 'an aggregation is pending: call lddl_bart_fill first'
+    out = torch.empty(n_out, dtype=torch.uint8, device='cuda')
+    co = torch.empty(n_chunks + 1, dtype=torch.int64, device='cuda')
+    nt = torch.empty(n_chunks, dtype=torch.int32, device='cuda')
+    dco = torch.empty(d.numel(), dtype=torch.int64, device='cuda')
+    check(lib.lddl_bart_fill(ctx._h, _stream(), _ptr(out), _ptr(co), _ptr(nt), _ptr(dco)))
+    assert small_chunks(out, co, nt, dco) == ref_aggregate(docs, 7)
+
+
+@needs_torch_arena
+def test_closing_the_context_returns_a_pending_aggregation():
+    from lddl_amd import punkt
+    from lddl_amd.context import Context
+    _, (t, s, d) = small_layout()
+    c = Context(VOCAB_UNCASED, True)
+    punkt.set_params(c, None)
+    before = allocated()
+    rc, n_chunks, _ = raw_bart_count(c, t, s, d, 4)
+    assert rc == 0 and n_chunks >= 2 and allocated() > before
+    c.close()  # between count and fill
+    assert allocated() == before

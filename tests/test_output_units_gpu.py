@@ -1,7 +1,7 @@
-"""The output stage's kernels (csrc/output.hip) one by one at their edge shapes: per-partition
-and single-segment binning against numpy's stable argsort / bincount, and the string / npy
-rendering of hand-built pair tables, every row against Python's ' '.join and np.save, with
-2-byte and 4-byte token ids."""
+"""The output stage's kernels one by one at their edge shapes: per-partition and single-segment
+binning (csrc/output_bin.hip) against numpy's stable argsort / bincount, and the string / npy
+rendering (csrc/output_render.hip) of hand-built pair tables, every row against Python's
+' '.join and np.save, with 2-byte and 4-byte token ids."""
 import io
 
 import numpy as np

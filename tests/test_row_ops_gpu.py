@@ -1,4 +1,4 @@
-"""The load balance's row-movement kernels (csrc/output.hip: take, ragged gather, segment
+"""The load balance's row-movement kernels (csrc/output_rows.hip: take, ragged gather, segment
 expansion, metadata pack / unpack), HipOps method by method against TorchCpuOps (the numpy
 restatement in balance_util.py) on the same inputs; and the C entry points' NULL row index (the
 identity), which HipOps never passes."""

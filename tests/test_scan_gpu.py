@@ -1,4 +1,5 @@
-"""The device-wide exclusive scan (csrc/scan.h, scan.hip) by itself against np.cumsum: wave and
+"""The device-wide exclusive scan (csrc/scan.h, and scan.hip with
+lddl_scan_i64) by itself against np.cumsum: wave and
 tile edges, the single-workgroup scan of the tile sums across its carry loop (more than 256
 tiles of 2048 elements), 64-bit values whose low halves carry into the high halves, and the
 functor instantiation behind HipOps.ragged_offsets against TorchCpuOps."""

@@ -1,6 +1,7 @@
-"""GPU Punkt segmentation parity (csrc/segment.hip through lddl_segment_count/_fill) against
-nltk's spans (tests/golden/punkt.npz) and the oracle, and the segmented path end to end
-(segment -> tokenize -> NSP pairs + static masking) against the oracle."""
+"""GPU Punkt segmentation parity (csrc/segment.hip through lddl_segment_count/_fill, with the
+tables of csrc/punkt.hip) against nltk's spans (tests/golden/punkt.npz) and the oracle, the
+segmented path end to end (segment -> tokenize -> NSP pairs + static masking) against the
+oracle, and the context's Punkt state: unset, pending, replaced, closed."""
 import json
 import os
 
@@ -172,3 +173,97 @@ def test_segment_blocks_balance(ctx, golden):
     assert allocated() == before
     so, ds = punkt.segment(ctx, text, doc_off)  # the context segments again after the cancel
     assert so.numel() - 1 == exp
+
+
+# ---- the context's Punkt state: unset, pending, replaced, closed -----------------------------
+
+SMALL_DOCS = ['Dr. Who came in. He sat down. Then he left.',
+              'It was e.g. a test. Mr. J. Smith spoke. The end.']
+
+
+def small_corpus():
+    """Two documents of three short sentences whose cuts the golden parameters change ('dr',
+    'e.g' and 'mr' are abbreviations there)."""
+    import torch
+    enc = [d.encode() for d in SMALL_DOCS]
+    doc_off = np.concatenate([[0], np.cumsum([len(e) for e in enc])]).astype(np.int64)
+    text = np.frombuffer(b''.join(enc), np.uint8)
+    return text, doc_off, torch.from_numpy(text.copy()).cuda(), torch.from_numpy(doc_off).cuda()
+
+
+def oracle_sentences(text, doc_off, params=None):
+    from oracle import oracle as O
+    st, en, cnt = O.Punkt(params).spans(text, doc_off)
+    return reference_sentences(text, doc_off, st, en, cnt)
+
+
+def raw_count(c, t, do):
+    """lddl_segment_count itself (punkt.segment sets the parameters when none were set)."""
+    import ctypes
+    from lddl_amd._native import lib
+    from lddl_amd.context import _ptr, _stream
+    n = ctypes.c_int64(-1)
+    rc = lib.lddl_segment_count(c._h, _stream(), _ptr(t), t.numel(), _ptr(do), do.numel() - 1,
+                                ctypes.byref(n))
+    return rc, n.value
+
+
+def test_count_needs_set_params_then_works():
+    from lddl_amd._native import lib
+    from lddl_amd.context import Context
+    text, doc_off, t, do = small_corpus()
+    c = Context(VOCAB_UNCASED, True)  # lddl_punkt_set_params never called
+    rc, _ = raw_count(c, t, do)
+    assert rc == -1
+    assert lib.lddl_last_error().decode() == 'Punkt parameters not set (lddl_punkt_set_params)'
+    assert gpu_sentences(c, text, doc_off) == oracle_sentences(text, doc_off)
+    c.close()
+
+
+def test_second_count_is_refused_and_the_fill_returns_the_first(ctx):
+    import torch
+    from lddl_amd import punkt
+    from lddl_amd._native import check, lib
+    from lddl_amd.context import _ptr, _stream
+    text, doc_off, t, do = small_corpus()
+    punkt.set_params(ctx, None)
+    rc, n_sent = raw_count(ctx, t, do)
+    assert rc == 0
+    # another batch: were it counted, the fill below would write its offsets
+    other = torch.from_numpy(np.frombuffer(b'One. Two. Three. Four. Five.', np.uint8).copy()).cuda()
+    rc2, _ = raw_count(ctx, other, torch.tensor([0, other.numel()]).cuda())
+    assert rc2 == -1
+    assert lib.lddl_last_error().decode() == 'a segmentation is pending: call lddl_segment_fill first'
+    so = torch.empty(n_sent + 1, dtype=torch.int64, device='cuda')
+    ds = torch.empty(do.numel(), dtype=torch.int64, device='cuda')
+    check(lib.lddl_segment_fill(ctx._h, _stream(), _ptr(so), _ptr(ds)))
+    assert punkt.stripped_sentences(text, so.cpu().numpy(), ds.cpu().numpy()) == \
+        oracle_sentences(text, doc_off)
+    assert lib.lddl_segment_fill(ctx._h, _stream(), _ptr(so), _ptr(ds)) == -1  # nothing pending
+    assert lib.lddl_last_error().decode() == 'no pending segmentation (lddl_segment_count)'
+
+
+def test_set_params_replaces_the_tables(ctx, golden):
+    """Trained parameters, then none: the tables of the first call are gone."""
+    text, doc_off, _, _ = small_corpus()
+    trained = gpu_sentences(ctx, text, doc_off, golden['params'])
+    assert trained == oracle_sentences(text, doc_off, golden['params'])
+    untrained = gpu_sentences(ctx, text, doc_off)
+    assert untrained == oracle_sentences(text, doc_off) and untrained != trained
+    got = gpu_sentences(ctx, golden['text'], golden['doc_off'])
+    assert got == reference_sentences(golden['text'], golden['doc_off'], golden['untrained_start'],
+                                      golden['untrained_end'], golden['untrained_count'])
+
+
+@needs_torch_arena
+def test_closing_the_context_returns_a_pending_segmentation(golden):
+    from lddl_amd import punkt
+    from lddl_amd.context import Context
+    _, _, t, do = small_corpus()
+    c = Context(VOCAB_UNCASED, True)
+    punkt.set_params(c, punkt.PunktParams.from_dict(golden['params']))
+    before = allocated()
+    rc, n_sent = raw_count(c, t, do)
+    assert rc == 0 and n_sent >= 2 and allocated() > before
+    c.close()  # between count and fill
+    assert allocated() == before
