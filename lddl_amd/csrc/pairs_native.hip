@@ -354,7 +354,8 @@ __device__ inline uint32_t lemire_below(uint32_t x, uint32_t n, CtrRng& rng) {
 // [MASK] below ceil(0.8 * 2^32), the original token below ceil(0.9 * 2^32), else a random token.
 constexpr uint32_t kNat80 = 3435973837u, kNat90 = 3865470567u;
 
-// Masked positions of 64 consecutive pairs per wave (one lane per pair), in lock step so that
+// Masked positions of ppw consecutive pairs per wave (one lane per pair; 64, or fewer where the
+// staged masks of 64 pairs exceed the LDS budget, the lanes above ppw idle), in lock step so that
 // every lane's Philox refill comes at the same iteration:
 //  1. Floyd's sampling of num candidate indices out of nc (a uniform num-subset: the shuffled
 //     prefix of pretrain.py:197-207), one draw per step, into a lane-private LDS bitmap;
@@ -364,19 +365,19 @@ constexpr uint32_t kNat80 = 3435973837u, kNat90 = 3865470567u;
 //     out with coalesced stores.
 // Every draw's stream position depends on the pair alone (the sampling and the decisions use
 // separate streams), so a pair's masks do not depend on the pairs that share its wave.
-__global__ void __launch_bounds__(256) mask_native_kernel(NativeArgs A, int32_t stage_cap) {
+__global__ void __launch_bounds__(256) mask_native_kernel(NativeArgs A, int32_t stage_cap, int32_t ppw) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_mn[];
   const int w = wave_id(), lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  const int64_t q0 = ((int64_t)blockIdx.x * nw + w) * 64;
+  const int64_t q0 = ((int64_t)blockIdx.x * nw + w) * ppw;
   if (q0 >= A.n_pairs) return;
   uint32_t* bm = reinterpret_cast<uint32_t*>(s_mn) + (size_t)w * A.words * 64 + lane;
   int32_t* stok = reinterpret_cast<int32_t*>(s_mn + (size_t)nw * A.words * 64 * 4) + (size_t)w * stage_cap;
   uint16_t* spos = reinterpret_cast<uint16_t*>(s_mn + (size_t)nw * A.words * 64 * 4 +
                                                 (size_t)nw * stage_cap * 4) + (size_t)w * stage_cap;
   const int64_t q = q0 + lane;
-  const bool valid = q < A.n_pairs;
+  const bool valid = lane < ppw && q < A.n_pairs;
   const int64_t qv = valid ? q : q0;
-  const int64_t qe = q0 + 64 < A.n_pairs ? q0 + 64 : A.n_pairs;
+  const int64_t qe = q0 + ppw < A.n_pairs ? q0 + ppw : A.n_pairs;
   const int64_t m0 = A.moff[q0];
   const int32_t mend = (int32_t)(A.moff[qe] - m0);
   const int32_t num = valid ? A.nmask[qv] : 0;
@@ -694,14 +695,22 @@ int plan_native(lddl_pairs* P, PlanWork& W) {
     A.mpos = P->mpos;
     A.mtok = P->mtok;
     A.words = (prm->seq + 31) / 32;
-    // per wave: the 64 lanes' bitmaps + the staged masks of its 64 pairs (<= max_pred each);
-    // up to 4 waves per workgroup within 64 KB of LDS
-    const int32_t stage_cap = 64 * std::max(P->max_pred, 1);
-    const size_t per_wave = (size_t)A.words * 64 * 4 + (size_t)stage_cap * 6;
+    // per wave: the 64 lanes' bitmaps + the staged masks of its ppw pairs (<= max_pred each);
+    // up to 4 waves per workgroup within 64 KB of LDS. 64 pairs per wave while their staging fits
+    // that budget, else half as many until it does (seq 4096 at ratio 0.15: 8; one pair of 4096
+    // masks, ratio 1.0, takes 56 KB). Sized for 64 pairs whatever the ratio, seq 512 at ratio 1.0
+    // (196 KB) or seq 2500 at 0.15 would ask for more LDS than a CU has
+    const int32_t mp = std::max(P->max_pred, 1);
+    auto wave_bytes = [&](int32_t pairs) { return (size_t)A.words * 64 * 4 + (size_t)pairs * mp * 6; };
+    int32_t ppw = 64;
+    while (ppw > 1 && wave_bytes(ppw) > 65536) ppw >>= 1;
+    const int32_t stage_cap = ppw * mp;
+    const size_t per_wave = wave_bytes(ppw);
     const int nwv = (int)std::max<size_t>(1, std::min<size_t>(4, 65536 / per_wave));
+    const int64_t per_wg = (int64_t)ppw * nwv;  // pairs per workgroup
     if (n && !prm->whole_word)
-      hipLaunchKernelGGL(mask_native_kernel, dim3((unsigned)((n + 64 * nwv - 1) / (64 * nwv))),
-                         dim3(64 * nwv), per_wave * nwv, st, A, stage_cap);
+      hipLaunchKernelGGL(mask_native_kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(64 * nwv),
+                         per_wave * nwv, st, A, stage_cap, ppw);
     if (n && prm->whole_word) {
       // one wave per pair; per wave an 8-byte entry per token of the longest pair (seq - 3,
       // rounded up to whole windows) and a ballot per window + 1; up to 4 waves within 64 KB
