@@ -1,9 +1,8 @@
 // The environment knobs the pair stage reads when a plan starts (check_plan_args, pairs_api.hip):
 // what each accepts and the message it is rejected with. (Host-only and free of the HIP runtime,
 // like plan_split.h, so a CPU program can test it: tests/pair_knobs_check.cpp.) The knobs read
-// later, where they apply, stay with their stages: LDDL_NATIVE_LDS_WORDS (pairs_native.hip),
-// LDDL_AMD_MASK_POOL and LDDL_PLAN_SLICE_DENSE (the replay planner, pairs.hip), LDDL_SHUFFLE_GLOBAL
-// (pairs_shuffle.hip).
+// later, where they apply, stay with their stages: LDDL_NATIVE_LDS_WORDS (pairs_native.hip) and
+// LDDL_SHUFFLE_GLOBAL (pairs_shuffle.hip).
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -34,27 +33,38 @@ inline int read_fy_knobs(FyKnobs* k) {
   return 0;
 }
 
-// Every knob of check_plan_args, in the order their messages have always come.
-//   LDDL_PLAN_SPLIT (A/B knob of the split replay plan): unset or -1 = automatic
+// Every knob of check_plan_args, read in the order their messages have always come.
+//   split (LDDL_PLAN_SPLIT, A/B knob of the split replay plan): unset or -1 = automatic
 //   (plan_split_point), 0 = one range, k > 0 = a head range of exactly min(k, n_part) partitions.
-//   LDDL_PLAN_SLICE (A/B knob of the time-sliced replay plan): unset or -1 = automatic
+//   slice (LDDL_PLAN_SLICE, A/B knob of the time-sliced replay plan): unset or -1 = automatic
 //   (plan_slice_on), 0 = never, k > 0 = always, with a quantum of k documents.
-//   LDDL_PLAN_WAVES (tests and A/B): the persistent grid of a sliced plan, g >= 1 workgroups
-//   (unset or -1: what the device holds at once).
-inline int read_plan_knobs(FyKnobs* fy, int64_t* split, int64_t* slice, int64_t* waves) {
-  *split = *slice = *waves = -1;
-  static const char kWavesMsg[] = "LDDL_PLAN_WAVES must be -1 (auto) or a workgroup count up to 2^20";
-  int rc;
-  if ((rc = read_int_knob("LDDL_PLAN_SPLIT", -1, "LDDL_PLAN_SPLIT must be -1 (auto), 0 or a partition count",
-                          split)) ||
-      (rc = read_int_knob("LDDL_PLAN_SLICE", -1,
-                          "LDDL_PLAN_SLICE must be -1 (auto), 0 or a quantum of documents", slice)) ||
-      (rc = read_int_knob("LDDL_PLAN_WAVES", -1, kWavesMsg, waves)))
-    return rc;
-  if (*waves == 0 || *waves > (1 << 20)) LDDL_FAIL(-1, "%s", kWavesMsg);
-  if (*split > 0 && *slice > 0)
+//   waves (LDDL_PLAN_WAVES, tests and A/B): the persistent grid of a sliced plan, g >= 1
+//   workgroups (unset or -1: what the device holds at once).
+//   slice_dense (LDDL_PLAN_SLICE_DENSE, A/B, 0 .. 2): who packs `dense` in a sliced plan.
+//   mask_pool (LDDL_AMD_MASK_POOL, tests): entries of the first attempt's mask pool, to force a
+//   re-plan (unset = -1: sized from the kept tokens).
+struct PlanKnobs {
+  int64_t split = -1, slice = -1, waves = -1, slice_dense = 1, mask_pool = -1;
+  FyKnobs fy;
+};
+
+inline int read_plan_knobs(PlanKnobs* k) {
+  *k = PlanKnobs{};
+  const struct { const char *name, *msg; int64_t lo, hi, *out; } ints[] = {
+      {"LDDL_PLAN_SPLIT", "LDDL_PLAN_SPLIT must be -1 (auto), 0 or a partition count", -1, INT64_MAX, &k->split},
+      {"LDDL_PLAN_SLICE", "LDDL_PLAN_SLICE must be -1 (auto), 0 or a quantum of documents", -1, INT64_MAX,
+       &k->slice},
+      {"LDDL_PLAN_WAVES", "LDDL_PLAN_WAVES must be -1 (auto) or a workgroup count up to 2^20", -1, 1 << 20,
+       &k->waves},
+      {"LDDL_PLAN_SLICE_DENSE", "LDDL_PLAN_SLICE_DENSE must be 0, 1 or 2", 0, 2, &k->slice_dense},
+      {"LDDL_AMD_MASK_POOL", "LDDL_AMD_MASK_POOL must be an entry count >= 0", 0, INT64_MAX, &k->mask_pool}};
+  for (const auto& e : ints) {
+    if (int rc = read_int_knob(e.name, e.lo, e.msg, e.out)) return rc;
+    if (*e.out > e.hi || (e.out == &k->waves && *e.out == 0)) LDDL_FAIL(-1, "%s", e.msg);
+  }
+  if (k->split > 0 && k->slice > 0)
     LDDL_FAIL(-1, "LDDL_PLAN_SPLIT and LDDL_PLAN_SLICE are both forced: a split plan is not sliced");
-  return read_fy_knobs(fy);
+  return read_fy_knobs(&k->fy);
 }
 
 }  // namespace lddl

@@ -1052,17 +1052,17 @@ int plan_replay_setup(lddl_pairs* P, PlanWork& W) {
   // tokens (expected use ~0.15 * 1.5 and ~1.5 times dup * tokens); a plan that outgrows them
   // reports the exact sizes and is planned again (deterministic replay)
   if ((rc = W.tmp.take(&W.pool_ctl, 4)) || (rc = P->mem.take(&P->part_base, n_part + 1))) return rc;
-  W.cap = W.jcap = 0;
+  PoolAttempt& L = W.pools;  // (no entries unless the plan masks)
   A.jbytes = prm->seq <= 256 ? 1 : 2;  // every draw j_i < nc <= seq - 3
   if (prm->masking && W.n_sent) {
-    W.cap = (int64_t)(2.0 * prm->masked_lm_ratio * prm->dup * (double)W.n_kept_tok) +
+    L.cap = (int64_t)(2.0 * prm->masked_lm_ratio * prm->dup * (double)W.n_kept_tok) +
             (int64_t)prm->dup * P->n_kept_sent / 2 + kPoolChunk * (n_part + 16);
-    W.jcap = (int64_t)(1.6 * prm->dup * (double)W.n_kept_tok) + 8 * slots +
+    L.jcap = (int64_t)(1.6 * prm->dup * (double)W.n_kept_tok) + 8 * slots +
              kPoolChunk * (n_part + 16);  // + the 16-entry alignment of every pair's draws
-    if (const char* e = getenv("LDDL_AMD_MASK_POOL")) W.cap = atoll(e);  // tests: force a re-plan
+    if (W.knobs.mask_pool >= 0) L.cap = W.knobs.mask_pool;  // tests: force a re-plan
   }
   // SlotPool keeps pool offsets as 32-bit multiples of 8 / 16 entries
-  if (W.cap / 8 >= (int64_t)UINT32_MAX || W.jcap / 16 >= (int64_t)UINT32_MAX)
+  if (L.cap / 8 >= (int64_t)UINT32_MAX || L.jcap / 16 >= (int64_t)UINT32_MAX)
     LDDL_FAIL(-1, "batch too large for the mask pools (split it into smaller GPU batches)");
   A.pool_used = W.pool_ctl;
   A.overflow = reinterpret_cast<int32_t*>(W.pool_ctl + 1);
@@ -1070,9 +1070,9 @@ int plan_replay_setup(lddl_pairs* P, PlanWork& W) {
 }
 
 typedef void (*PlanKernel)(PlanArgs);
-static PlanKernel planner_kernel(const PlanWork& W) {
+static PlanKernel planner_kernel(const PlanWork& W, bool sliced) {
   const bool docs_lds = W.max_docs + 1 <= (unsigned long long)kDocLds;  // document table in LDS
-  if (W.sliced)
+  if (sliced)
     return docs_lds ? (W.A.jbytes == 1 ? plan_replay_kernel<true, 1, true> : plan_replay_kernel<true, 2, true>)
                     : (W.A.jbytes == 1 ? plan_replay_kernel<false, 1, true> : plan_replay_kernel<false, 2, true>);
   return docs_lds ? (W.A.jbytes == 1 ? plan_replay_kernel<true, 1> : plan_replay_kernel<true, 2>)
@@ -1080,62 +1080,42 @@ static PlanKernel planner_kernel(const PlanWork& W) {
 }
 constexpr size_t kPlanLds = 4 * (kN + kLook) + 4 * (kDocLds + 4) + 16;  // ~4.8 KB: 7 waves/SIMD fit
 
-// The head range of a split replay plan with static masking (0: one range): what the device
-// holds of the planner's one-wave workgroups at once, see plan_split_point.
-// planner workgroups (one wave each) the device holds at once, for the instantiation W selects
-static int planner_capacity(const PlanWork& W, int64_t* capacity) {
-  int per_cu = 0, n_cu = 0;
-  LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, planner_kernel(W), 64, kPlanLds));
-  LDDL_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, W.c->device));
-  *capacity = (int64_t)per_cu * n_cu;
-  return 0;
-}
-
-int choose_split(const PlanWork& W, int64_t* s) {
-  *s = 0;
-  if (W.sliced || !W.prm->masking || W.n_part <= 0 || W.split_knob == 0) return 0;
-  int64_t capacity = 0;
-  int rc;
-  if (W.split_knob < 0 && (rc = planner_capacity(W, &capacity))) return rc;
-  *s = plan_split_point(W.n_part, capacity, W.split_knob);
-  return 0;
-}
-
-// Whether the plan runs time-sliced in one range (plan_slice_on; with or without masking; a
-// forced split keeps the split path), and then its grid, ring and save areas.
-int choose_slice(const lddl_pairs* P, PlanWork& W) {
-  W.sliced = false;
-  if (W.n_part <= 0 || W.split_knob > 0 || W.slice_knob == 0) return 0;
-  if (W.slice_knob < 0 && !kPlanSliceAuto) return 0;
-  int64_t capacity = 0;
-  int rc;
-  W.sliced = true;  // (the capacity of the sliced instantiation)
-  rc = planner_capacity(W, &capacity);
-  W.sliced = !rc && plan_slice_on(W.n_part, capacity, W.slice_knob);
-  if (rc || !W.sliced) return rc;
-  W.sl_grid = std::min<int64_t>(W.n_part, W.waves_knob > 0 ? W.waves_knob : std::max<int64_t>(capacity, 1));
-  W.sl_dense = env_int("LDDL_PLAN_SLICE_DENSE", 1);
-  if (W.sl_dense < 0 || W.sl_dense > 2) LDDL_FAIL(-1, "LDDL_PLAN_SLICE_DENSE must be 0, 1 or 2");
+// The plan's mode (plan_replay_mode, plan_split.h: one shot, time-sliced or split at W.split.s)
+// and what follows from the decision to slice: the grid, the ring and the save areas.
+int choose_mode(const lddl_pairs* P, PlanWork& W) {
+  // planner workgroups (one wave each) the device holds at once, of either instantiation
+  auto capacity_of = [&W](bool sliced, int64_t* capacity) {
+    int per_cu = 0, n_cu = 0;
+    LDDL_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, planner_kernel(W, sliced), 64, kPlanLds));
+    LDDL_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, W.c->device));
+    *capacity = (int64_t)per_cu * n_cu;
+    return 0;
+  };
+  ReplayMode m;
+  int rc = plan_replay_mode(W.n_part, W.prm->masking != 0, W.knobs.split, W.knobs.slice, capacity_of, &m);
+  SlicePlan& S = W.slice;
+  S.on = m.sliced;
+  W.split.s = m.split;
+  if (rc || !S.on) return rc;
+  S.grid = std::min<int64_t>(W.n_part, W.knobs.waves > 0 ? W.knobs.waves : std::max<int64_t>(m.capacity, 1));
   const unsigned __int128 units = (unsigned __int128)(uint64_t)W.prm->dup * (uint64_t)P->n_kept_doc;
-  W.sl_ring_cap = plan_slice_ring_entries(
-      W.n_part, units > (unsigned __int128)INT64_MAX ? INT64_MAX : (int64_t)units, W.slice_knob);
+  S.ring_cap = plan_slice_ring_entries(
+      W.n_part, units > (unsigned __int128)INT64_MAX ? INT64_MAX : (int64_t)units, W.knobs.slice);
   // tickets and dense-group claims are 32-bit counters
-  if (W.sl_ring_cap >= INT32_MAX - W.n_part || P->n_kept_sent / 64 >= INT32_MAX - (int64_t)(1 << 24))
+  if (S.ring_cap >= INT32_MAX - W.n_part || P->n_kept_sent / 64 >= INT32_MAX - (int64_t)(1 << 24))
     LDDL_FAIL(-1, "batch too large for the time-sliced plan (LDDL_PLAN_SLICE=0, or smaller GPU batches)");
-  uint64_t* save;
-  if ((rc = W.tmp.take(&W.sl_queue, 4 + ((W.sl_ring_cap + 3) & ~(int64_t)3))) ||
-      (rc = W.tmp.take(&save, W.n_part * kSaveU64)))
-    return rc;
   PlanArgs& A = W.A;
-  A.sl_ctl = W.sl_queue;
-  A.sl_ring = W.sl_queue + 4;
-  A.sl_save = save;
-  A.sl_ring_cap = (int32_t)W.sl_ring_cap;
-  A.sl_dense = W.sl_dense == 1;
-  A.sl_quantum = (int32_t)std::min<int64_t>(std::max<int64_t>(W.slice_knob, 0), INT32_MAX);
+  if ((rc = W.tmp.take(&S.queue, 4 + ((S.ring_cap + 3) & ~(int64_t)3))) ||
+      (rc = W.tmp.take(&A.sl_save, W.n_part * kSaveU64)))
+    return rc;
+  A.sl_ctl = S.queue;
+  A.sl_ring = S.queue + 4;
+  A.sl_ring_cap = (int32_t)S.ring_cap;
+  A.sl_dense = W.knobs.slice_dense == 1;
+  A.sl_quantum = (int32_t)std::min<int64_t>(std::max<int64_t>(W.knobs.slice, 0), INT32_MAX);
 #ifdef LDDL_STAMPS
-  if ((rc = W.tmp.take(&W.d_tls, 2 * (W.n_part + W.sl_ring_cap)))) return rc;
-  LDDL_HIP(hipMemsetAsync(W.d_tls, 0, 16 * (W.n_part + W.sl_ring_cap), W.st));
+  if ((rc = W.tmp.take(&W.d_tls, 2 * (W.n_part + S.ring_cap)))) return rc;
+  LDDL_HIP(hipMemsetAsync(W.d_tls, 0, 16 * (W.n_part + S.ring_cap), W.st));
   A.tls = W.d_tls;
 #endif
   return 0;
@@ -1145,21 +1125,46 @@ int choose_slice(const lddl_pairs* P, PlanWork& W) {
 // takes `mpos` here, at the pool's capacity: mpos shares the mask pool's index space, and the
 // head's mask replay fills it while the tail range still allocates from the pool.
 static int take_pools(lddl_pairs* P, PlanWork& W, bool split) {
-  W.mtok_try = nullptr;
-  W.jpool_try = nullptr;
+  PoolAttempt& L = W.pools;
+  L.mtok_try = nullptr;
+  L.jpool_try = nullptr;
   int rc;
   if (W.prm->masking) {
     LDDL_HIP(hipMemsetAsync(W.pool_ctl, 0, 32, W.st));
-    if ((rc = P->mem.take(&W.mtok_try, W.cap + 4)) ||
-        (rc = W.tmp.take(&W.jpool_try, W.A.jbytes * (W.jcap + 16))))
+    if ((rc = P->mem.take(&L.mtok_try, L.cap + 4)) ||
+        (rc = W.tmp.take(&L.jpool_try, W.A.jbytes * (L.jcap + 16))) ||
+        (split && (rc = P->mem.take(&P->mpos, L.cap + 4))))
       return rc;
-    if (split && (rc = P->mem.take(&P->mpos, W.cap + 4))) return rc;
   }
-  W.A.mtok = W.mtok_try;
-  W.A.jpool = W.jpool_try;
-  W.A.pool_cap = W.cap;
-  W.A.jpool_cap = W.jcap;
+  W.A.mtok = L.mtok_try;
+  W.A.jpool = L.jpool_try;
+  W.A.pool_cap = L.cap;
+  W.A.jpool_cap = L.jcap;
   return 0;
+}
+
+// The attempt stands: its blocks are the plan's. One range takes `mpos` now, at its exact size.
+static int adopt_pools(lddl_pairs* P, PlanWork& W, const unsigned long long ctl[4]) {
+  P->mtok = W.pools.mtok_try;
+  W.jpool = W.pools.jpool_try;
+  return W.split.s ? 0 : P->mem.take(&P->mpos, (int64_t)ctl[0]);
+}
+
+// The attempt is void: its blocks go back, with `mpos` and a split plan's head tables (laid out on them).
+void drop_pools(lddl_pairs* P, PlanWork& W) {
+  PairRange& h = P->rg[0];
+  for (void* b : {(void*)W.pools.mtok_try, (void*)P->mpos, (void*)h.rec, (void*)h.tok_off, (void*)h.pos_off})
+    if (b) P->mem.give(b);
+  W.tmp.give(W.pools.jpool_try);
+  P->mtok = nullptr;
+  P->mpos = nullptr;
+  W.jpool = nullptr;
+  h = PairRange{};
+}
+
+void grow_pools(PlanWork& W, const unsigned long long ctl[4]) {  // exactly what this attempt needed
+  W.pools.cap = (int64_t)ctl[0] + 1024;
+  W.pools.jcap = (int64_t)ctl[2] + 1024;
 }
 
 // One plan_replay_kernel launch over partitions [p0, p0 + n) on `st`. with_dense: its extra
@@ -1171,77 +1176,64 @@ static int launch_planner(const PlanWork& W, int64_t p0, int64_t n, hipStream_t 
   A.n_part = (int32_t)n;
   A.dense_lo = dense_lo;
   if (!with_dense) A.n_kept_sent = 0;
-  if (W.sliced) {
+  if (W.slice.on) {
     // The whole plan by the persistent grid. `dense` is packed by the waves that leave the queue
     // (the default), or by densify_kernel behind (LDDL_PLAN_SLICE_DENSE=0) or ahead of the
     // planner (2): the one-shot launch's tail, which hides that work, no longer exists.
     auto densify = [&]() {
-      if (A.n_kept_sent)
-        launch_densify(A.ks_start, A.ks_len, A.kscan, A.n_kept_sent, A.ids, A.dense, st);
+      if (A.n_kept_sent) launch_densify(A.ks_start, A.ks_len, A.kscan, A.n_kept_sent, A.ids, A.dense, st);
     };
-    LDDL_HIP(hipMemsetAsync(W.sl_queue, 0, 4 * (4 + ((W.sl_ring_cap + 3) & ~(int64_t)3)), st));
-    if (W.sl_dense == 2) densify();
-    hipLaunchKernelGGL(planner_kernel(W), dim3((unsigned)W.sl_grid), dim3(64), kPlanLds, st, A);
-    if (W.sl_dense == 0) densify();
-    LDDL_HIP(hipGetLastError());
-    return 0;
+    LDDL_HIP(hipMemsetAsync(W.slice.queue, 0, 4 * (4 + ((W.slice.ring_cap + 3) & ~(int64_t)3)), st));
+    if (W.knobs.slice_dense == 2) densify();
+    hipLaunchKernelGGL(planner_kernel(W, true), dim3((unsigned)W.slice.grid), dim3(64), kPlanLds, st, A);
+    if (W.knobs.slice_dense == 0) densify();
+  } else if (const unsigned grid = (unsigned)n + (A.n_kept_sent ? (unsigned)A.n_dense_wg : 0u)) {
+    hipLaunchKernelGGL(planner_kernel(W, false), dim3(grid), dim3(64), kPlanLds, st, A);
   }
-  const unsigned grid = (unsigned)n + (A.n_kept_sent ? (unsigned)A.n_dense_wg : 0u);
-  if (grid) hipLaunchKernelGGL(planner_kernel(W), dim3(grid), dim3(64), kPlanLds, st, A);
   LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
+// The planner's one sync per range, partitions [p0, p0 + n): pairs per partition -> their first
+// pairs in `table` (table[n], the range's pair count, to *n_pairs) and the largest count
+// (W.max_np), read back with the pool counters (ctl) and one more copy (x_dst null: none).
+static int read_back_range(PlanWork& W, int64_t p0, int64_t n, int64_t* table, int64_t* n_pairs,
+                           unsigned long long ctl[4], void* x_dst = nullptr, const void* x_src = nullptr,
+                           size_t x_bytes = 0) {
+  hipStream_t st = W.st;
+  if (!W.prm->masking) LDDL_HIP(hipMemsetAsync(W.pool_ctl, 0, 32, st));
+  LDDL_HIP(scan_exclusive(Identity{W.part_npairs + p0}, n, table, W.scratch, st));
+  hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs + p0, n, W.pool_ctl + 3);
+  LDDL_HIP(hipGetLastError());
+  LDDL_HIP(hipMemcpyAsync(ctl, W.pool_ctl, 32, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipMemcpyAsync(n_pairs, table + n, 8, hipMemcpyDeviceToHost, st));
+  if (x_dst) LDDL_HIP(hipMemcpyAsync(x_dst, x_src, x_bytes, hipMemcpyDeviceToHost, st));
+  LDDL_HIP(hipStreamSynchronize(st));
+  W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
   return 0;
 }
 
 // One range: launches plan_replay_kernel (between the plan's two events) and, when a pool
 // overflowed, once more with the exact sizes. attempt 1: the re-plan of a split plan.
 int plan_replay_unsplit(lddl_pairs* P, PlanWork& W, int attempt) {
-  const lddl_pair_params* prm = W.prm;
-  const int64_t n_part = W.n_part;
-  hipStream_t st = W.st;
   int rc;
-  for (; n_part; ++attempt) {
+  for (; W.n_part; ++attempt) {
     if ((rc = take_pools(P, W, false))) return rc;
-    LDDL_HIP(hipEventRecord(P->ev[0], st));
-    if ((rc = launch_planner(W, 0, n_part, st, true, nullptr))) return rc;
-    LDDL_HIP(hipEventRecord(P->ev[1], st));
-    // pairs per partition -> output offsets and the largest count, read back with the pool
-    // counters in the planner's one sync
-    if (!prm->masking) LDDL_HIP(hipMemsetAsync(W.pool_ctl, 0, 32, st));
-    LDDL_HIP(scan_exclusive(Identity{W.part_npairs}, n_part, P->part_base, W.scratch, st));
-    hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs, n_part, W.pool_ctl + 3);
+    LDDL_HIP(hipEventRecord(P->ev[0], W.st));
+    if ((rc = launch_planner(W, 0, W.n_part, W.st, true, nullptr))) return rc;
+    LDDL_HIP(hipEventRecord(P->ev[1], W.st));
     unsigned long long ctl[4];
-    LDDL_HIP(hipMemcpyAsync(ctl, W.pool_ctl, 32, hipMemcpyDeviceToHost, st));
-    LDDL_HIP(hipMemcpyAsync(&P->n_pairs, P->part_base + n_part, 8, hipMemcpyDeviceToHost, st));
     unsigned sl_ctl[4] = {0, 0, 0, 0};
-    if (W.sliced) LDDL_HIP(hipMemcpyAsync(sl_ctl, W.sl_queue, 16, hipMemcpyDeviceToHost, st));
-    LDDL_HIP(hipStreamSynchronize(st));
+    if ((rc = read_back_range(W, 0, W.n_part, P->part_base, &P->n_pairs, ctl, W.slice.on ? sl_ctl : nullptr,
+                              W.slice.queue, 16)))
+      return rc;
     P->n_slices = sl_ctl[1];
-    W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
-    if (!prm->masking) break;
-    if (!ctl[1]) {
-      P->mtok = W.mtok_try;
-      W.jpool = W.jpool_try;
-      if ((rc = P->mem.take(&P->mpos, (int64_t)ctl[0]))) return rc;
-      break;
-    }
-    P->mem.give(W.mtok_try);
-    W.tmp.give(W.jpool_try);
+    if (!W.prm->masking) break;
+    if (!ctl[1]) return adopt_pools(P, W, ctl);
+    drop_pools(P, W);
     if (attempt > 0) LDDL_FAIL(-1, "mask pool overflow after resize");
-    W.cap = (int64_t)ctl[0] + 1024;
-    W.jcap = (int64_t)ctl[2] + 1024;
+    grow_pools(W, ctl);
   }
-  return 0;
-}
-
-// The context's side stream for the tail range: non-blocking (the caller's stream may be the
-// null stream) and of the lowest priority, so the head range's workgroups are placed first.
-static int plan_side_stream(lddl_ctx* c, hipStream_t* out) {
-  if (!c->plan_side) {
-    int least = 0, greatest = 0;
-    LDDL_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    LDDL_HIP(hipStreamCreateWithPriority(&c->plan_side, hipStreamNonBlocking, least));
-  }
-  *out = c->plan_side;
   return 0;
 }
 
@@ -1249,19 +1241,27 @@ static int plan_side_stream(lddl_ctx* c, hipStream_t* out) {
 // [s, n_part) on the side stream, both allocating from the same pools. The tail launch keeps the
 // dense-packing workgroups for its kept sentences; the head's are packed by densify_head_kernel,
 // first on the caller's stream after the head planner (by then every tail workgroup that fits is
-// resident). Returns after the head's sync with rg[0].n_pairs and *usable = no pool overflow so
-// far (else the head's slots may point past the pools and nothing downstream may run on them).
+// resident). Returns after the head's sync with rg[0] = [0, s), its n_pairs, and *usable = no pool
+// overflow so far: the pools then stand unless the tail overflows them (else the head's slots may
+// point past the pools, nothing downstream may run on them, and the range counts no pairs).
 int plan_replay_split_head(lddl_pairs* P, PlanWork& W, bool* usable) {
-  const int64_t n_part = W.n_part, s = W.split;
-  hipStream_t st = W.st, side;
+  SplitPlan& S = W.split;
+  const int64_t n_part = W.n_part, s = S.s;
   int rc;
-  if ((rc = plan_side_stream(W.c, &side)) || (rc = take_pools(P, W, true)) ||
-      (rc = W.tmp.take(&W.split_info, 2)) || (rc = W.tmp.take(&W.tail_rel, n_part - s + 1)))
+  // the context's side stream for the tail range: non-blocking (the caller's stream may be the
+  // null stream) and of the lowest priority, so the head range's workgroups are placed first
+  if (!W.c->plan_side) {
+    int least = 0, greatest = 0;
+    LDDL_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    LDDL_HIP(hipStreamCreateWithPriority(&W.c->plan_side, hipStreamNonBlocking, least));
+  }
+  hipStream_t st = W.st, side = W.c->plan_side;
+  if ((rc = take_pools(P, W, true)) || (rc = W.tmp.take(&S.info, 2)) ||
+      (rc = W.tmp.take(&S.tail_rel, n_part - s + 1)))
     return rc;
   LDDL_HIP(hipEventCreateWithFlags(&P->ev_fork, hipEventDisableTiming));
   LDDL_HIP(hipEventCreateWithFlags(&P->ev_join, hipEventDisableTiming));
-  hipLaunchKernelGGL(split_info_kernel, dim3(1), dim3(1), 0, st, P->kp_off, P->kd_off, P->kscan, s,
-                     W.split_info);
+  hipLaunchKernelGGL(split_info_kernel, dim3(1), dim3(1), 0, st, P->kp_off, P->kd_off, P->kscan, s, S.info);
   LDDL_HIP(hipGetLastError());
   LDDL_HIP(hipEventRecord(P->ev[0], st));
   // the side stream starts after the compaction (and everything else queued on st so far)
@@ -1269,52 +1269,34 @@ int plan_replay_split_head(lddl_pairs* P, PlanWork& W, bool* usable) {
   LDDL_HIP(hipStreamWaitEvent(side, P->ev_fork, 0));
   if ((rc = launch_planner(W, 0, s, st, false, nullptr))) return rc;
   P->tail_pending = true;  // (from here every return path joins before a block goes back)
-  rc = launch_planner(W, s, n_part - s, side, true, W.split_info);
+  rc = launch_planner(W, s, n_part - s, side, true, S.info);
   LDDL_HIP(hipEventRecord(P->ev_join, side));
   if (rc) return rc;
   if (P->n_kept_sent)
     hipLaunchKernelGGL(densify_head_kernel, dim3((unsigned)((P->n_kept_sent + 255) / 256)), dim3(256),
-                       0, st, P->ks_start, P->ks_len, P->kscan, W.split_info, W.d_ids, P->dense);
-  LDDL_HIP(scan_exclusive(Identity{W.part_npairs}, s, P->part_base, W.scratch, st));
-  hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs, s, W.pool_ctl + 3);
-  LDDL_HIP(hipGetLastError());
+                       0, st, P->ks_start, P->ks_len, P->kscan, S.info, W.d_ids, P->dense);
   unsigned long long ctl[4];
-  LDDL_HIP(hipMemcpyAsync(ctl, W.pool_ctl, 32, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipMemcpyAsync(&P->rg[0].n_pairs, P->part_base + s, 8, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipMemcpyAsync(W.h_split_info, W.split_info, 16, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipStreamSynchronize(st));
-  W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
+  if ((rc = read_back_range(W, 0, s, P->part_base, &P->rg[0].n_pairs, ctl, S.h_info, S.info, 16))) return rc;
+  P->rg[0].p1 = s;
   *usable = ctl[1] == 0;
-  return 0;
+  if (!*usable) P->rg[0].n_pairs = 0;
+  return *usable ? adopt_pools(P, W, ctl) : 0;
 }
 
-// Split plan, second half: joins the tail range on the planning stream and reads back in one sync
-// its pair count (rg[1].n_pairs; W.tail_rel: its partitions' first pairs), the largest partition
-// (W.max_np) and the pool counters (ctl[1] != 0: a pool overflowed).
+// Split plan, second half: joins the tail range on the planning stream and reads it back
+// (rg[1].n_pairs; W.split.tail_rel: its partitions' first pairs; ctl[1] != 0: a pool overflowed).
 int plan_replay_split_tail(lddl_pairs* P, PlanWork& W, unsigned long long ctl[4]) {
-  hipStream_t st = W.st;
-  const int64_t s = W.split, n_tail = W.n_part - s;
-  P->join(st);
-  LDDL_HIP(hipEventRecord(P->ev[1], st));
-  LDDL_HIP(scan_exclusive(Identity{W.part_npairs + s}, n_tail, W.tail_rel, W.scratch, st));
-  hipLaunchKernelGGL(max_pairs_kernel, dim3(64), dim3(256), 0, st, W.part_npairs + s, n_tail,
-                     W.pool_ctl + 3);
-  LDDL_HIP(hipGetLastError());
-  LDDL_HIP(hipMemcpyAsync(ctl, W.pool_ctl, 32, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipMemcpyAsync(&P->rg[1].n_pairs, W.tail_rel + n_tail, 8, hipMemcpyDeviceToHost, st));
-  LDDL_HIP(hipStreamSynchronize(st));
-  W.max_np = std::max<int64_t>(1, (int64_t)ctl[3]);
-  return 0;
+  P->join(W.st);
+  LDDL_HIP(hipEventRecord(P->ev[1], W.st));
+  return read_back_range(W, W.split.s, W.n_part - W.split.s, W.split.tail_rel, &P->rg[1].n_pairs, ctl);
 }
 
 // The tail range's partitions in the plan's table of first output pairs, behind the head's.
 int tail_part_base(lddl_pairs* P, PlanWork& W) {
-  hipStream_t st = W.st;
-  const int64_t s = W.split, n_tail = W.n_part - s;
-  const PairRange& h = P->rg[0];
+  const int64_t s = W.split.s, n_tail = W.n_part - s;
   if (n_tail)
     hipLaunchKernelGGL(tail_part_base_kernel, dim3((unsigned)((n_tail + 255) / 256)), dim3(256), 0,
-                       st, W.tail_rel, n_tail, h.n_pairs, P->part_base + s);
+                       W.st, W.split.tail_rel, n_tail, P->rg[0].n_pairs, P->part_base + s);
   LDDL_HIP(hipGetLastError());
   return 0;
 }
@@ -1371,8 +1353,8 @@ int report_plan_stamps(const PlanWork& W) {
     fprintf(stderr, " %.1f", (t[2 * q] - t0) / 1e5);
   }
   fprintf(stderr, "\n");
-  if (W.sliced) {  // the slices (one per ticket): how many waves were planning in every bin
-    const int64_t n_tk = n_part + W.sl_ring_cap;
+  if (W.slice.on) {  // the slices (one per ticket): how many waves were planning in every bin
+    const int64_t n_tk = n_part + W.slice.ring_cap;
     std::vector<uint64_t> ts(2 * n_tk);
     LDDL_HIP(hipMemcpyAsync(ts.data(), W.d_tls, 16 * n_tk, hipMemcpyDeviceToHost, st));
     LDDL_HIP(hipStreamSynchronize(st));
@@ -1382,7 +1364,7 @@ int report_plan_stamps(const PlanWork& W) {
     std::sort(sl.begin(), sl.end());
     if (!sl.empty())
       fprintf(stderr, "[timeline] %zu slices on %lld waves, slice ms min %.2f p50 %.2f p90 %.2f max %.2f\n",
-              sl.size(), (long long)W.sl_grid, sl[0], sl[sl.size() / 2], sl[sl.size() * 9 / 10], sl.back());
+              sl.size(), (long long)W.slice.grid, sl[0], sl[sl.size() / 2], sl[sl.size() * 9 / 10], sl.back());
     fprintf(stderr, "[timeline] active waves (slices) per %.2f ms bin:", span / nb);
     for (int b = 0; b < nb; ++b) {
       const uint64_t a = t0 + (t1 - t0) * b / nb, e = t0 + (t1 - t0) * (b + 1) / nb;

@@ -3,10 +3,11 @@
 // launches no kernel of its own. Each stage's kernels and the host function that launches them
 // are one unit:
 //   pairs_plan.h       the records the stages share, the plan's state, the stage functions
-//   pair_knobs.h       the environment knobs read when a plan starts (host-only)
+//   pair_knobs.h       every environment knob of a plan, read when it starts (host-only)
+//   plan_split.h       the replay plan's host decisions: its mode, the split point, the ring
 //   pairs_compact.hip  compaction of the tokenizer's output (compact_inputs)
-//   pairs.hip          the replay planner: one-range, time-sliced and split plans (it keeps the
-//                      file, and with it the history of the code most changes touch)
+//   pairs.hip          the replay planner; its mode, an attempt's pools and a range's read-back (it
+//                      keeps the file, and with it the history of the code most changes touch)
 //   pairs_native.hip   the native planner and its mask kernels (plan_native)
 //   pairs_shuffle.hip  the replay plan's partition shuffle (shuffle_partitions)
 //   pairs_layout.hip   gather records, output-order scans, mask replay (layout_*)
@@ -44,8 +45,7 @@ using namespace lddl;
 // static masking: the gather keeps a decision per token of the sequence in LDS (pairs_gather.hip)
 constexpr int kMaxSeqGather = 4096;
 
-static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKnobs* fy, int64_t* split_knob,
-                           int64_t* slice_knob, int64_t* waves_knob) {
+static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, PlanKnobs* knobs) {
   if (!c || !prm) LDDL_FAIL(-1, "null argument");
   if (prm->seq < 5 || prm->seq > 65535) LDDL_FAIL(-1, "target_seq_length %d out of range", prm->seq);
   if (prm->dup < 1) LDDL_FAIL(-1, "duplicate_factor must be >= 1");
@@ -60,7 +60,7 @@ static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, FyKno
   if (prm->whole_word && prm->rng != LDDL_RNG_NATIVE)
     LDDL_FAIL(-1, "whole_word needs rng = LDDL_RNG_NATIVE (the replay mode reproduces the "
                   "reference, which has no whole-word masking)");
-  return read_plan_knobs(fy, split_knob, slice_knob, waves_knob);
+  return read_plan_knobs(knobs);
 }
 
 // Everything downstream of the planner for a one-range replay plan. Without masking, pair_prep
@@ -77,15 +77,6 @@ static int finish_unsplit(lddl_pairs* P, PlanWork& W) {
   if ((rc = report_plan_stamps(W))) return rc;
 #endif
   return P->masking ? layout_replay(P, W, r) : layout_pairs(P, W);
-}
-
-// a range's shuffle and layout temporaries, when the next range (or the re-plan) takes its own
-static void give_range_tmp(PlanWork& W) {
-  for (void* b : {(void*)W.M.slots, (void*)W.M.dstq, (void*)W.pcnt, (void*)W.scr2})
-    if (b) W.tmp.give(b);
-  W.M = PairMaps{nullptr, nullptr, nullptr, nullptr};
-  W.pcnt = nullptr;
-  W.scr2 = nullptr;
 }
 
 static int32_t max_predictions(const lddl_pair_params* prm) {
@@ -107,28 +98,21 @@ static int plan_head_stage(lddl_pairs* P, const int64_t* d_sent_off, const int32
   if (W.prm->rng == LDDL_RNG_NATIVE) {
     if ((rc = plan_native(P, W))) return rc;
   } else {
-    if ((rc = plan_replay_setup(P, W)) || (rc = choose_slice(P, W)) || (rc = choose_split(W, &W.split)))
-      return rc;
-    if (!W.split) {
+    if ((rc = plan_replay_setup(P, W)) || (rc = choose_mode(P, W))) return rc;
+    if (!W.split.s) {
       if ((rc = plan_replay_unsplit(P, W, 0)) || (rc = finish_unsplit(P, W))) return rc;
     } else {
       bool usable = false;
       if ((rc = plan_replay_split_head(P, W, &usable))) return rc;
       PairRange& r = P->rg[0];
-      r.p1 = W.split;
       if (usable) {
-        // (the pools of this attempt stand unless the tail overflows them)
-        W.jpool = W.jpool_try;
-        P->mtok = W.mtok_try;
         if ((rc = shuffle_partitions(P, W, r, P->part_base)) || (rc = layout_replay(P, W, r))) return rc;
         P->head_valid = true;
-      } else {
-        r.n_pairs = 0;
       }
     }
   }
   LDDL_HIP(hipStreamSynchronize(W.st));  // the ranges' totals (layout_scan)
-  if (!W.split) {
+  if (!W.split.s) {
     P->n_tokens = P->rg[0].n_tokens;
     P->n_masked = P->rg[0].n_masked;
     P->work.reset();
@@ -142,45 +126,35 @@ static int plan_head_stage(lddl_pairs* P, const int64_t* d_sent_off, const int32
 static int plan_tail_stage(lddl_pairs* P) {
   if (!P->work) return 0;
   PlanWork& W = *P->work;
-  hipStream_t st = W.st;
-  const int64_t s = W.split;
   int rc;
   unsigned long long ctl[4];
   PairRange &h = P->rg[0], &t = P->rg[1];
   if ((rc = plan_replay_split_tail(P, W, ctl))) return rc;
-  if (ctl[1]) {  // a pool overflowed: the head's output is void; one range, exact sizes
+  // the head's shuffle and layout temporaries: the tail range (or the re-plan) takes its own
+  for (void* b : {(void*)W.rt.M.slots, (void*)W.rt.M.dstq, (void*)W.rt.pcnt, (void*)W.rt.scr2})
+    if (b) W.tmp.give(b);
+  W.rt = RangeTmp{};
+  if (ctl[1]) {  // a pool overflowed: the head's output is void; one range (h), exact sizes
     P->head_valid = false;
-    give_range_tmp(W);
-    for (void* b : {(void*)W.mtok_try, (void*)P->mpos, (void*)h.rec, (void*)h.tok_off, (void*)h.pos_off})
-      if (b) P->mem.give(b);
-    W.tmp.give(W.jpool_try);
-    P->mtok = nullptr;
-    P->mpos = nullptr;
-    W.jpool = nullptr;
-    h = PairRange{};
+    drop_pools(P, W);
+    grow_pools(W, ctl);
     t = PairRange{};
-    W.split = 0;
-    W.cap = (int64_t)ctl[0] + 1024;
-    W.jcap = (int64_t)ctl[2] + 1024;
+    W.split.s = 0;
     if ((rc = plan_replay_unsplit(P, W, 1)) || (rc = finish_unsplit(P, W))) return rc;
-    LDDL_HIP(hipStreamSynchronize(st));
-    P->n_tokens = h.n_tokens;
-    P->n_masked = h.n_masked;
   } else {
-    give_range_tmp(W);
     if ((rc = tail_part_base(P, W))) return rc;
-    t.p0 = s;
+    t.p0 = W.split.s;
     t.p1 = W.n_part;
     t.pair0 = h.n_pairs;
     t.tok0 = h.n_tokens;
     t.pos0 = h.n_masked;
     P->n_rg = 2;
-    if ((rc = shuffle_partitions(P, W, t, W.tail_rel)) || (rc = layout_replay(P, W, t))) return rc;
-    LDDL_HIP(hipStreamSynchronize(st));
-    P->n_pairs = h.n_pairs + t.n_pairs;
-    P->n_tokens = h.n_tokens + t.n_tokens;
-    P->n_masked = h.n_masked + t.n_masked;
+    if ((rc = shuffle_partitions(P, W, t, W.split.tail_rel)) || (rc = layout_replay(P, W, t))) return rc;
   }
+  LDDL_HIP(hipStreamSynchronize(W.st));
+  P->n_pairs = h.n_pairs + t.n_pairs;
+  P->n_tokens = h.n_tokens + t.n_tokens;
+  P->n_masked = h.n_masked + t.n_masked;
   P->work.reset();
   return 0;
 }
@@ -201,11 +175,10 @@ extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_p
                                     const int64_t* d_part_doc_off, const int64_t* d_part_seed,
                                     int64_t n_part, lddl_pairs** out, int64_t* head) {
   if (out) *out = nullptr;
-  FyKnobs fy;
-  int64_t split_knob, slice_knob, waves_knob;
+  PlanKnobs knobs;
   int rc;
   if (!out) LDDL_FAIL(-1, "null argument");
-  if ((rc = check_plan_args(c, prm, &fy, &split_knob, &slice_knob, &waves_knob))) return rc;
+  if ((rc = check_plan_args(c, prm, &knobs))) return rc;
   hipStream_t st = as_stream(stream);
   // until it is handed out, an error return drops the plan: its blocks go back on `st` (after
   // the tail launch, when one is in flight)
@@ -219,8 +192,7 @@ extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_p
   P->max_pred = max_predictions(prm);
   LDDL_HIP(hipEventCreate(&P->ev[0]));
   LDDL_HIP(hipEventCreate(&P->ev[1]));
-  P->work.reset(new PlanWork{c, &P->prm, d_ids, d_part_seed, n_sent, n_part, st, P->mem, fy, split_knob,
-                              slice_knob, waves_knob});
+  P->work.reset(new PlanWork(c, &P->prm, d_ids, d_part_seed, n_sent, n_part, st, P->mem, knobs));
   if ((rc = plan_head_stage(P.get(), d_sent_off, d_sent_len, d_doc_sent_off, n_doc, d_part_doc_off)))
     return rc;
   if (head) {
@@ -232,9 +204,7 @@ extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_p
       head[1] = h.n_pairs;
       head[2] = h.n_tokens;
       head[3] = h.n_masked;
-      head[4] = plan_suggest_capacity(h.n_pairs, W.n_kept_tok, W.h_split_info[1]);
-      head[5] = plan_suggest_capacity(h.n_tokens, W.n_kept_tok, W.h_split_info[1]);
-      head[6] = plan_suggest_capacity(h.n_masked, W.n_kept_tok, W.h_split_info[1]);
+      for (int i = 4; i < 7; ++i) head[i] = plan_suggest_capacity(head[i - 3], W.n_kept_tok, W.split.h_info[1]);
     }
     head[7] = P->n_slices;
   }

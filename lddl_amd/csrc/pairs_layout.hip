@@ -292,12 +292,12 @@ __global__ void __launch_bounds__(64) fy_resolve_kernel(ResolveArgs R) {
 }  // namespace
 
 // The gather records + output-order scans (tok_off, pos_off) of the plan's pairs.
-// (of one range; W.pcnt / W.scr2 are the range's temporaries)
+// (of one range; W.rt.pcnt / W.rt.scr2 are the range's temporaries)
 static int layout_alloc(lddl_pairs* P, PlanWork& W, PairRange& r) {
   const int64_t npairs = r.n_pairs;
   int rc;
   if ((rc = P->mem.take(&r.tok_off, npairs + 1)) || (rc = P->mem.take(&r.rec, npairs)) ||
-      (rc = W.tmp.take(&W.pcnt, npairs)) || (rc = W.tmp.take(&W.scr2, 2 * scan_scratch_elems(npairs))))
+      (rc = W.tmp.take(&W.rt.pcnt, npairs)) || (rc = W.tmp.take(&W.rt.scr2, 2 * scan_scratch_elems(npairs))))
     return rc;
   if (P->masking && (rc = P->mem.take(&r.pos_off, npairs + 1))) return rc;
   return 0;
@@ -306,9 +306,9 @@ static int layout_alloc(lddl_pairs* P, PlanWork& W, PairRange& r) {
 // tok_off (and pos_off) from the counts, then the range's totals (read with the caller's sync)
 static int layout_scan(lddl_pairs* P, PlanWork& W, PairRange& r) {
   if (P->masking)
-    LDDL_HIP(scan_exclusive2(PairCounts{W.pcnt}, r.n_pairs, r.tok_off, r.pos_off, W.scr2, W.st));
+    LDDL_HIP(scan_exclusive2(PairCounts{W.rt.pcnt}, r.n_pairs, r.tok_off, r.pos_off, W.rt.scr2, W.st));
   else
-    LDDL_HIP(scan_exclusive(PairTokens{W.pcnt}, r.n_pairs, r.tok_off, W.scr2, W.st));
+    LDDL_HIP(scan_exclusive(PairTokens{W.rt.pcnt}, r.n_pairs, r.tok_off, W.rt.scr2, W.st));
   LDDL_HIP(hipMemcpyAsync(&r.n_tokens, r.tok_off + r.n_pairs, 8, hipMemcpyDeviceToHost, W.st));
   if (P->masking)
     LDDL_HIP(hipMemcpyAsync(&r.n_masked, r.pos_off + r.n_pairs, 8, hipMemcpyDeviceToHost, W.st));
@@ -326,7 +326,7 @@ int layout_pairs(lddl_pairs* P, PlanWork& W) {
   if (npairs)
     hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, W.st,
                        P->src, npairs, P->desc, P->kscan, P->masking ? P->nmask : nullptr,
-                       P->moff, r.rec, W.pcnt);
+                       P->moff, r.rec, W.rt.pcnt);
   LDDL_HIP(hipGetLastError());
   return layout_scan(P, W, r);
 }
@@ -336,10 +336,10 @@ int layout_pairs(lddl_pairs* P, PlanWork& W) {
 static int resolve_masks(lddl_pairs* P, PlanWork& W, const PairRange& r) {
   if (!r.n_pairs) return 0;
   const int32_t seq = P->seq;
-  const FyKnobs& fy = W.fy;
+  const FyKnobs& fy = W.knobs.fy;
   hipStream_t st = W.st;
-  ResolveArgs RA{W.M.slots, r.n_pairs, P->desc, W.spool, W.jpool, P->mpos, P->kscan, P->dense,
-                 P->cls_id, P->sep_id, W.M.dstq, r.rec, W.pcnt, 0};
+  ResolveArgs RA{W.rt.M.slots, r.n_pairs, P->desc, W.spool, W.jpool, P->mpos, P->kscan, P->dense,
+                 P->cls_id, P->sep_id, W.rt.M.dstq, r.rec, W.rt.pcnt, 0};
   // a lane's column covers the padded draw region (steps up to nc rounded up to 16)
   const size_t col = (size_t)((seq + 15) & ~15);
   RA.col_rows = (int32_t)col;

@@ -1,11 +1,11 @@
 // What the units of the pair stage share (pairs.hip, pairs_*.hip): the records the stages hand
-// to each other, the plan's state, and the host functions of each stage. Kernels and their device
-// helpers are private to their unit (an anonymous namespace there, as in collate_dev.h); the types
-// here appear in the stage functions' signatures, so they live in namespace lddl proper.
+// to each other, the plan's state (PlanWork, with a struct of its own for a replay plan's pools,
+// slice, split and range temporaries), and the host functions of each stage. Kernels and their
+// device helpers are private to their unit (an anonymous namespace there, as in collate_dev.h);
+// the types here appear in the stage functions' signatures, so they live in namespace lddl proper.
 #pragma once
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <memory>
 
 #include "common.h"
@@ -130,6 +130,30 @@ struct alignas(16) GatherRec {
   int32_t na, nb_rn, nm, pad;
 };
 
+// The mask pools of one planning attempt; take_, adopt_, drop_ and grow_pools (pairs.hip) are its
+// four ends. An attempt that overflows a pool reports the exact sizes for the next one.
+struct PoolAttempt {
+  int64_t cap = 0, jcap = 0;    // entries: decisions, shuffle draws
+  int32_t* mtok_try = nullptr;  // this attempt's blocks
+  uint8_t* jpool_try = nullptr;
+};
+struct SlicePlan {  // the time-sliced plan (one range)
+  bool on = false;
+  unsigned* queue = nullptr;       // 4 control words + the ring, zeroed before every launch
+  int64_t ring_cap = 0, grid = 0;  // the ring's entries; the persistent grid
+};
+struct SplitPlan {          // (means something only while s != 0)
+  int64_t s = 0;            // partitions of the head range (0: one range)
+  int64_t* info = nullptr;  // split_info_kernel's two values, and their host copies
+  int64_t h_info[2] = {0, 0};
+  int64_t* tail_rel = nullptr;  // the tail partitions' first pairs, relative to the range
+};
+struct RangeTmp {  // a range's temporaries: shuffle_partitions (M), layout_* (pcnt, scr2)
+  PairMaps M{nullptr, nullptr, nullptr, nullptr};
+  int2* pcnt = nullptr;
+  int64_t* scr2 = nullptr;
+};
+
 // What one planning stage hands to the next: the inputs of the call, host values read back, and
 // device temporaries that no later call on the plan reads. The temporaries come from `tmp`,
 // today the plan's own scope (they live until lddl_pairs_destroy); a scope local to
@@ -143,10 +167,11 @@ struct PlanWork {
   int64_t n_sent, n_part;
   hipStream_t st;
   ArenaScope& tmp;
-  FyKnobs fy;
-  int64_t split_knob = -1;  // LDDL_PLAN_SPLIT
-  int64_t slice_knob = -1;  // LDDL_PLAN_SLICE
-  int64_t waves_knob = -1;  // LDDL_PLAN_WAVES
+  PlanKnobs knobs;
+  PlanWork(lddl_ctx* c, const lddl_pair_params* prm, const int32_t* d_ids, const int64_t* d_part_seed,
+           int64_t n_sent, int64_t n_part, hipStream_t st, ArenaScope& tmp, const PlanKnobs& knobs)
+      : c(c), prm(prm), d_ids(d_ids), d_part_seed(d_part_seed), n_sent(n_sent), n_part(n_part), st(st),
+        tmp(tmp), knobs(knobs) {}
   // compact_inputs
   int64_t* scratch = nullptr;  // scan scratch of the compaction and of the re-plan loop
   int64_t n_kept_tok = 0;
@@ -157,27 +182,13 @@ struct PlanWork {
   SlotPool* spool = nullptr;
   void* jpool = nullptr;
   int64_t max_np = 1;  // pairs of the largest partition
-  // the planner launch and its pools, kept for the tail call and the re-plan
+  // the planner launch, kept for the tail call and the re-plan
   PlanArgs A{};
   unsigned long long* pool_ctl = nullptr;  // [0] masks used, [1] overflow flag, [2] draws used, [3] max pairs
-  int64_t cap = 0, jcap = 0;
-  int32_t* mtok_try = nullptr;  // this attempt's pools
-  uint8_t* jpool_try = nullptr;
-  int64_t split = 0;            // partitions of the head range (0: one range)
-  int64_t* split_info = nullptr;  // split_info_kernel's two values, and their host copies
-  int64_t h_split_info[2] = {0, 0};
-  int64_t* tail_rel = nullptr;  // the tail partitions' first pairs, relative to the range
-  // the time-sliced plan (one range): the queue block (4 control words + the ring, zeroed before
-  // every launch), the partitions' save areas and the persistent grid
-  bool sliced = false;
-  unsigned* sl_queue = nullptr;
-  int64_t sl_ring_cap = 0, sl_grid = 0;
-  int sl_dense = 1;  // LDDL_PLAN_SLICE_DENSE (A/B): who packs `dense`, see launch_planner
-  // shuffle_partitions
-  PairMaps M{nullptr, nullptr, nullptr, nullptr};
-  // layout
-  int2* pcnt = nullptr;
-  int64_t* scr2 = nullptr;
+  PoolAttempt pools;
+  SlicePlan slice;
+  SplitPlan split;
+  RangeTmp rt;
 #ifdef LDDL_STAMPS
   uint64_t *d_stamps = nullptr, *d_tl = nullptr, *d_tls = nullptr;
 #endif
@@ -284,8 +295,9 @@ int compact_inputs(lddl_pairs* P, PlanWork& W, const int64_t* d_sent_off, const 
 int plan_native(lddl_pairs* P, PlanWork& W);
 // pairs.hip (the replay planner)
 int plan_replay_setup(lddl_pairs* P, PlanWork& W);
-int choose_slice(const lddl_pairs* P, PlanWork& W);
-int choose_split(const PlanWork& W, int64_t* s);
+int choose_mode(const lddl_pairs* P, PlanWork& W);
+void drop_pools(lddl_pairs* P, PlanWork& W);
+void grow_pools(PlanWork& W, const unsigned long long ctl[4]);
 int plan_replay_unsplit(lddl_pairs* P, PlanWork& W, int attempt);
 int plan_replay_split_head(lddl_pairs* P, PlanWork& W, bool* usable);
 int plan_replay_split_tail(lddl_pairs* P, PlanWork& W, unsigned long long ctl[4]);

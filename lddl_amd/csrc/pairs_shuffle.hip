@@ -177,7 +177,7 @@ int shuffle_partitions(lddl_pairs* P, PlanWork& W, const PairRange& r, const int
   const int64_t n_part = r.p1 - r.p0;
   hipStream_t st = W.st;
   int rc;
-  PairMaps& M = W.M;
+  PairMaps& M = W.rt.M;
   M = PairMaps{rel_base, nullptr, nullptr, nullptr};
   if (prm->masking) {
     if ((rc = W.tmp.take(&M.slots, r.n_pairs)) || (rc = W.tmp.take(&M.dstq, r.n_pairs))) return rc;

@@ -1,8 +1,9 @@
-// The host decisions of the replay plan's two large-batch forms (pairs.hip). The split plan:
-// where the planner's partitions are cut into a head and a tail range, and how large the
-// caller's output buffers should be when only the head's counts are known. The time-sliced plan:
-// whether to slice, the quantum and the hand-off ring's size. (Host-only and free of the HIP
-// runtime, so a CPU program can test it: tests/plan_split_check.cpp, tests/plan_slice_check.cpp.)
+// The host decisions of the replay plan (pairs.hip). Its mode: one range in one shot, one range
+// time-sliced, or a head and a tail range (plan_replay_mode, the one place that knows the
+// precedence). The split plan: where the partitions are cut, and how large the caller's output
+// buffers should be when only the head's counts are known. The time-sliced plan: whether to
+// slice, the quantum and the hand-off ring's size. (Host-only and free of the HIP runtime, so a
+// CPU program can test it: tests/plan_split_check.cpp, tests/plan_slice_check.cpp.)
 #pragma once
 #include <cstdint>
 
@@ -92,6 +93,35 @@ inline int64_t plan_slice_ring_entries(int64_t n_part, int64_t units_total, int6
   v += 16;
   const unsigned __int128 lim = (unsigned __int128)INT64_MAX;
   return (int64_t)(v > lim ? lim : v);
+}
+
+// ---- the mode of a replay plan: one range in one shot, time-sliced, or split ----
+struct ReplayMode {
+  bool sliced = false;
+  int64_t split = 0;     // partitions of the head range (0: one range); never with `sliced`
+  int64_t capacity = 0;  // of the sliced instantiation, where it was asked (it sizes the grid)
+};
+
+// The precedence: a forced split beats slicing, slicing beats the automatic split, no masking
+// means no split, a split is never sliced. capacity_of(bool sliced, int64_t* capacity) is the
+// occupancy query of either planner instantiation (non-zero: an error, handed through with *m at
+// one range); each is asked at most once and only where its answer is used: the sliced one
+// whenever the knobs allow slicing, the one-shot one for the automatic split.
+template <typename CapacityOf>
+inline int plan_replay_mode(int64_t n_part, bool masking, int64_t split_knob, int64_t slice_knob,
+                            CapacityOf&& capacity_of, ReplayMode* m) {
+  *m = ReplayMode{};
+  int64_t capacity = 0;  // (a forced split point takes none)
+  int rc;
+  if (n_part > 0 && split_knob <= 0 && slice_knob != 0 && (slice_knob > 0 || kPlanSliceAuto)) {
+    if ((rc = capacity_of(true, &capacity))) return rc;
+    m->sliced = plan_slice_on(n_part, capacity, slice_knob);
+    m->capacity = capacity;
+  }
+  if (m->sliced || !masking || n_part <= 0 || split_knob == 0) return 0;
+  if (split_knob < 0 && (rc = capacity_of(false, &capacity))) return rc;
+  m->split = plan_split_point(n_part, capacity, split_knob);
+  return 0;
 }
 
 }  // namespace lddl

@@ -12,6 +12,7 @@
 #include "pair_knobs.h"
 
 using lddl::FyKnobs;
+using lddl::PlanKnobs;
 using lddl::read_plan_knobs;
 
 #define EXPECT(c)                                                    \
@@ -22,13 +23,14 @@ using lddl::read_plan_knobs;
     }                                                                \
   } while (0)
 
-static const char* const kAll[] = {"LDDL_PLAN_SPLIT", "LDDL_PLAN_SLICE", "LDDL_PLAN_WAVES", "LDDL_FY_MODE",
-                                   "LDDL_FY_LW",      "LDDL_FY_RA",      "LDDL_FY_PF"};
+static const char* const kAll[] = {"LDDL_PLAN_SPLIT", "LDDL_PLAN_SLICE", "LDDL_PLAN_WAVES",
+                                   "LDDL_PLAN_SLICE_DENSE", "LDDL_AMD_MASK_POOL", "LDDL_FY_MODE",
+                                   "LDDL_FY_LW", "LDDL_FY_RA", "LDDL_FY_PF"};
 
 struct Knobs {
   int rc;
   FyKnobs fy;
-  int64_t split, slice, waves;
+  int64_t split, slice, waves, dense, pool;
 };
 
 // the knobs as a plan would read them with the environment {name = value, ...} (null: unset)
@@ -38,9 +40,11 @@ static Knobs read_with(const char* n0, const char* v0, const char* n1 = nullptr,
   if (n0 && v0) setenv(n0, v0, 1);
   if (n1 && v1) setenv(n1, v1, 1);
   if (n2 && v2) setenv(n2, v2, 1);
-  Knobs k{0, FyKnobs{99, 99, 99, 99}, 99, 99, 99};
-  k.rc = read_plan_knobs(&k.fy, &k.split, &k.slice, &k.waves);
-  return k;
+  PlanKnobs p;
+  p.split = p.slice = p.waves = p.slice_dense = p.mask_pool = 99;
+  p.fy = FyKnobs{99, 99, 99, 99};
+  const int rc = read_plan_knobs(&p);
+  return Knobs{rc, p.fy, p.split, p.slice, p.waves, p.slice_dense, p.mask_pool};
 }
 
 static bool rejected(const Knobs& k, const char* msg) {
@@ -50,6 +54,8 @@ static bool rejected(const Knobs& k, const char* msg) {
 static const char kSplitMsg[] = "LDDL_PLAN_SPLIT must be -1 (auto), 0 or a partition count";
 static const char kSliceMsg[] = "LDDL_PLAN_SLICE must be -1 (auto), 0 or a quantum of documents";
 static const char kWavesMsg[] = "LDDL_PLAN_WAVES must be -1 (auto) or a workgroup count up to 2^20";
+static const char kDenseMsg[] = "LDDL_PLAN_SLICE_DENSE must be 0, 1 or 2";
+static const char kPoolMsg[] = "LDDL_AMD_MASK_POOL must be an entry count >= 0";
 static const char kBothMsg[] = "LDDL_PLAN_SPLIT and LDDL_PLAN_SLICE are both forced: a split plan is not sliced";
 static const char kRaPfMsg[] =
     "LDDL_FY_RA / PF select 16-lane branch-free variants (not with LDDL_FY_MODE=0 or LDDL_FY_LW=32)";
@@ -60,6 +66,7 @@ int main() {
     const Knobs k = read_with(nullptr, nullptr);
     EXPECT(k.rc == 0 && k.split == -1 && k.slice == -1 && k.waves == -1);
     EXPECT(k.fy.mode == -1 && k.fy.lw == 16 && k.fy.ra == 1 && k.fy.pf == 4);
+    EXPECT(k.dense == 1 && k.pool == -1);  // the waves that leave the queue; the pool sized by the plan
   }
   // ---- LDDL_PLAN_SPLIT and LDDL_PLAN_SLICE: -1, 0 or a count; a whole decimal number ----
   const struct {
@@ -86,6 +93,31 @@ int main() {
   }
   for (const char* bad : {"0", "-2", "1048577", "x"})
     EXPECT(rejected(read_with("LDDL_PLAN_WAVES", bad), kWavesMsg));
+  // ---- LDDL_PLAN_SLICE_DENSE: 0, 1 or 2; LDDL_AMD_MASK_POOL: an entry count ----
+  for (int64_t v : {int64_t(0), int64_t(1), int64_t(2)}) {
+    char text[32];
+    snprintf(text, sizeof text, "%lld", (long long)v);
+    const Knobs k = read_with("LDDL_PLAN_SLICE_DENSE", text);
+    EXPECT(k.rc == 0 && k.dense == v && k.pool == -1 && k.split == -1 && k.slice == -1 && k.waves == -1);
+  }
+  for (const char* bad : {"x", "", "-1", "3", "1x"})
+    EXPECT(rejected(read_with("LDDL_PLAN_SLICE_DENSE", bad), kDenseMsg));
+  for (int64_t v : {int64_t(0), int64_t(100), int64_t(1) << 40}) {
+    char text[32];
+    snprintf(text, sizeof text, "%lld", (long long)v);
+    const Knobs k = read_with("LDDL_AMD_MASK_POOL", text);
+    EXPECT(k.rc == 0 && k.pool == v && k.dense == 1 && k.split == -1 && k.slice == -1 && k.waves == -1);
+  }
+  for (const char* bad : {"x", "", "-5", "-1", "100x"})
+    EXPECT(rejected(read_with("LDDL_AMD_MASK_POOL", bad), kPoolMsg));
+  // (their messages come after LDDL_PLAN_WAVES', dense before pool, and before LDDL_FY_*')
+  EXPECT(rejected(read_with("LDDL_PLAN_SLICE_DENSE", "3", "LDDL_PLAN_WAVES", "0"), kWavesMsg));
+  EXPECT(rejected(read_with("LDDL_AMD_MASK_POOL", "x", "LDDL_PLAN_WAVES", "x"), kWavesMsg));
+  EXPECT(rejected(read_with("LDDL_AMD_MASK_POOL", "x", "LDDL_PLAN_SLICE_DENSE", "x"), kDenseMsg));
+  EXPECT(rejected(read_with("LDDL_FY_MODE", "2", "LDDL_PLAN_SLICE_DENSE", "3"), kDenseMsg));
+  EXPECT(rejected(read_with("LDDL_FY_MODE", "2", "LDDL_AMD_MASK_POOL", "-5"), kPoolMsg));
+  // (and, malformed, before the conflict of the two forced knobs)
+  EXPECT(rejected(read_with("LDDL_PLAN_SPLIT", "2", "LDDL_PLAN_SLICE", "3", "LDDL_AMD_MASK_POOL", ""), kPoolMsg));
   // ---- a forced split is not sliced; "one range" may be ----
   EXPECT(rejected(read_with("LDDL_PLAN_SPLIT", "2", "LDDL_PLAN_SLICE", "3"), kBothMsg));
   {

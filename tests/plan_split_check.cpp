@@ -88,6 +88,62 @@ int main() {
     EXPECT(plan_suggest_capacity(INT64_MAX, INT64_MAX, 1) == INT64_MAX);
     EXPECT(plan_suggest_capacity(INT64_MAX, 0, 0) == INT64_MAX);
   }
+  // ---- the mode of a replay plan ----
+  // The rules, written out here on their own: sliced iff there are partitions, no split is forced,
+  // slicing is not off, and it is forced or (automatic, enabled) the sliced capacity is >= 2 and
+  // below the partitions; else split (masking, partitions, the knob not 0) at the forced head or
+  // half the one-shot capacity when that is >= 2 and below the partitions; else one range. Each
+  // capacity is asked at most once and only where it is used.
+  {
+    const int64_t caps[] = {0, 1, 2, 7, 16, 40};
+    for (int64_t n = 0; n <= 40; ++n)
+      for (int64_t c_shot : caps)
+        for (int64_t c_sliced : caps)
+          for (int masking = 0; masking < 2; ++masking)
+            for (int64_t split_knob : {int64_t(-1), int64_t(0), int64_t(1), int64_t(5), int64_t(100)})
+              for (int64_t slice_knob : {int64_t(-1), int64_t(0), int64_t(1), int64_t(9)}) {
+                if (split_knob > 0 && slice_knob > 0) continue;  // (refused by the knob parser)
+                int asked[2] = {0, 0};
+                auto capacity_of = [&](bool sliced, int64_t* capacity) {
+                  ++asked[sliced];
+                  *capacity = sliced ? c_sliced : c_shot;
+                  return 0;
+                };
+                lddl::ReplayMode m;
+                m.sliced = true;
+                m.split = 77;
+                EXPECT(lddl::plan_replay_mode(n, masking != 0, split_knob, slice_knob, capacity_of, &m) == 0);
+                const bool may_slice = n > 0 && split_knob <= 0 && slice_knob != 0;
+                const bool ask_sliced = may_slice && (slice_knob > 0 || lddl::kPlanSliceAuto);
+                const bool want_sliced =
+                    ask_sliced && (slice_knob > 0 || (c_sliced >= 2 && c_sliced < n));
+                const bool may_split = !want_sliced && masking && n > 0 && split_knob != 0;
+                int64_t want_split = 0;
+                if (may_split && split_knob > 0) want_split = split_knob < n ? split_knob : n;
+                if (may_split && split_knob < 0 && c_shot >= 2 && c_shot < n) want_split = c_shot / 2;
+                EXPECT(m.sliced == want_sliced);
+                EXPECT(m.split == want_split);
+                EXPECT(!(m.sliced && m.split));
+                EXPECT(m.capacity == (ask_sliced ? c_sliced : 0));  // (handed on: not asked twice)
+                EXPECT(asked[1] == (ask_sliced ? 1 : 0));
+                EXPECT(asked[0] == (may_split && split_knob < 0 ? 1 : 0));
+              }
+    // an error of the query comes back as it is, with the mode at one range
+    for (int fail_sliced = 0; fail_sliced < 2; ++fail_sliced) {
+      auto failing = [&](bool sliced, int64_t* capacity) {
+        *capacity = 7;
+        return sliced == (fail_sliced != 0) ? -42 : 0;
+      };
+      lddl::ReplayMode m;
+      m.sliced = true;
+      m.split = 77;
+      m.capacity = 77;
+      // 40 partitions, capacity 7, everything automatic: the sliced query comes first; with
+      // slicing off, the one-shot query decides the split
+      EXPECT(lddl::plan_replay_mode(40, true, -1, fail_sliced ? -1 : 0, failing, &m) == -42);
+      EXPECT(!m.sliced && m.split == 0 && m.capacity == 0);
+    }
+  }
   printf("plan_split_check ok\n");
   return 0;
 }

@@ -1,5 +1,6 @@
-"""The split plan's host decisions (csrc/plan_split.h: where the planner's partitions are cut, and
-the output capacities predicted from the head range) on the CPU: tests/plan_split_check.cpp is
+"""The split plan's host decisions (csrc/plan_split.h: where the planner's partitions are cut, the
+output capacities predicted from the head range, and which mode a replay plan runs in:
+plan_replay_mode) on the CPU: tests/plan_split_check.cpp is
 compiled with AddressSanitizer + UBSan and run as a plain executable."""
 import os
 import shutil
