@@ -1,8 +1,7 @@
 // The environment knobs the pair stage reads when a plan starts (check_plan_args, pairs_api.hip):
 // what each accepts and the message it is rejected with. (Host-only and free of the HIP runtime,
-// like plan_split.h, so a CPU program can test it: tests/pair_knobs_check.cpp.) The knobs read
-// later, where they apply, stay with their stages: LDDL_NATIVE_LDS_WORDS (pairs_native.hip) and
-// LDDL_SHUFFLE_GLOBAL (pairs_shuffle.hip).
+// like plan_split.h, so a CPU program can test it: tests/pair_knobs_check.cpp.) No stage reads a
+// knob of its own: each takes its values from PlanWork::knobs.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -43,8 +42,13 @@ inline int read_fy_knobs(FyKnobs* k) {
 //   slice_dense (LDDL_PLAN_SLICE_DENSE, A/B, 0 .. 2): who packs `dense` in a sliced plan.
 //   mask_pool (LDDL_AMD_MASK_POOL, tests): entries of the first attempt's mask pool, to force a
 //   re-plan (unset = -1: sized from the kept tokens).
+//   native_lds_words (LDDL_NATIVE_LDS_WORDS, tests): the cap on the LDS words of the native
+//   planner's walk tables, so that the global-prefix path runs (unset = -1: kNativeLdsWordsCap).
+//   shuffle_global (LDDL_SHUFFLE_GLOBAL, tests): set at all, whatever the value, forces the
+//   partition shuffle's large-partition (global-memory) path.
 struct PlanKnobs {
-  int64_t split = -1, slice = -1, waves = -1, slice_dense = 1, mask_pool = -1;
+  int64_t split = -1, slice = -1, waves = -1, slice_dense = 1, mask_pool = -1, native_lds_words = -1;
+  bool shuffle_global = false;
   FyKnobs fy;
 };
 
@@ -57,11 +61,14 @@ inline int read_plan_knobs(PlanKnobs* k) {
       {"LDDL_PLAN_WAVES", "LDDL_PLAN_WAVES must be -1 (auto) or a workgroup count up to 2^20", -1, 1 << 20,
        &k->waves},
       {"LDDL_PLAN_SLICE_DENSE", "LDDL_PLAN_SLICE_DENSE must be 0, 1 or 2", 0, 2, &k->slice_dense},
-      {"LDDL_AMD_MASK_POOL", "LDDL_AMD_MASK_POOL must be an entry count >= 0", 0, INT64_MAX, &k->mask_pool}};
+      {"LDDL_AMD_MASK_POOL", "LDDL_AMD_MASK_POOL must be an entry count >= 0", 0, INT64_MAX, &k->mask_pool},
+      {"LDDL_NATIVE_LDS_WORDS", "LDDL_NATIVE_LDS_WORDS must be a word count >= 0", 0, INT64_MAX,
+       &k->native_lds_words}};
   for (const auto& e : ints) {
     if (int rc = read_int_knob(e.name, e.lo, e.msg, e.out)) return rc;
     if (*e.out > e.hi || (e.out == &k->waves && *e.out == 0)) LDDL_FAIL(-1, "%s", e.msg);
   }
+  k->shuffle_global = getenv("LDDL_SHUFFLE_GLOBAL") != nullptr;
   if (k->split > 0 && k->slice > 0)
     LDDL_FAIL(-1, "LDDL_PLAN_SPLIT and LDDL_PLAN_SLICE are both forced: a split plan is not sliced");
   return read_fy_knobs(&k->fy);

@@ -1,598 +1,31 @@
 // Pair stage, the replay planner (LDDL_RNG_REPLAY; the stage's other units and its orchestration:
-// file map in pairs_api.hip): CPython's MT19937 wave-uniform (WaveRng), the
-// sentence-length window (LenWin), plan_replay_kernel with its time-sliced queue, the dense
-// packing that runs in the planner's shadow (densify_*), and the host side of one-range, sliced
-// and split plans (lddl/dask/bert/pretrain.py:161-176, 182-238, 241-365, 386-402).
+// file map in pairs_api.hip): plan_replay_kernel, the three one-purpose kernels beside it and the
+// host side of one-range, sliced and split plans (lddl/dask/bert/pretrain.py:161-176, 182-238,
+// 241-365, 386-402). The kernel's device pieces are headers: CPython's MT19937 wave-uniform
+// (replay_rng.h), the sentence-length window (replay_len.h), the time-sliced queue
+// (replay_slice.h) and one wave's share of the dense packing (densify_dev.h).
 #include <cstdio>
+#include <type_traits>
 #include <vector>
 
+#include "densify_dev.h"
 #include "pairs_plan.h"
+#include "replay_len.h"
+#include "replay_rng.h"
+#include "replay_slice.h"
 
 namespace lddl {
 namespace {
 
-// ---------------------------------------------------------------------------------------------
-// Wave-uniform CPython MT19937 (Modules/_randommodule.c).
-// Raw state and the tempered 624-word block live in LDS; draws are served from a register
-// window (lane l holds word wbase+l) through readlane, so a draw costs a few instructions.
-// Every lane executes the same sequential algorithm with identical scalars (uniform control
-// flow); only parallel phases (twist, temper, speculative shuffle draws) use the lanes.
-// ---------------------------------------------------------------------------------------------
-constexpr int kN = 624, kM = 397;
-constexpr int kLook = 64;  // MT words of look-ahead past the block (WaveRng)
 constexpr int64_t kPoolChunk = 4096;  // mask pool entries reserved per atomic
-
-__device__ inline int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ inline uint32_t rdlane(uint32_t v, int idx) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, uni(idx));
-}
-__device__ inline uint32_t temper(uint32_t y) {
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680u;
-  y ^= (y << 15) & 0xefc60000u;
-  y ^= (y >> 18);
-  return y;
-}
-
-struct WaveRng {
-  // LDS: the raw 624-word block followed by kLook words of look-ahead, the next block's first
-  // words (next[i] = twist1(cur[i], cur[i+1], cur[i+397]) for i < 227 depends on the current
-  // block alone). mti indexes that extended stream: a window starting at mti < 624 may read up to
-  // kLook words past it without a block check, and the twist runs when a window or a register
-  // refill starts at mti >= 624 (mti -= 624 afterwards).
-  uint32_t* mt;
-  int mti;       // next word (uniform), < kN + kLook
-  int wbase;     // register window base (uniform)
-  int wend;      // wbase + 64 while the register window is valid, 0 when stale (uniform)
-  uint32_t win;  // this lane's tempered word temper(mt[wbase + lane])
-#ifdef LDDL_STAMPS
-  uint64_t n_pass = 0, n_win = 0;  // diagnostics: Jacobi passes / Fisher-Yates windows
-#endif
-
-  __device__ static uint32_t twist1(uint32_t a, uint32_t b, uint32_t c) {
-    const uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
-    return c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-  }
-
-  // Regenerate the block in place with all 64 lanes: ten straight-line rounds of 64 consecutive
-  // words (no exec-mask loops), then the look-ahead. Word i reads old[i], old[i+1] and old[i+397]
-  // (i < 227) or new[i-227], written three rounds earlier; a round reads before it writes, and
-  // one wave's LDS operations complete in order, so the rounds need only a compiler fence. Word
-  // 623 reads "old[624]" = the look-ahead word 0 = new[0] (seed_i64 sets it for the first block);
-  // round 9's lanes past 623 write scratch into the look-ahead, which the last round overwrites.
-  __device__ void twist() {
-    const int l = threadIdx.x;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      const int i = 64 * r + l;
-      const int ci = r < 3 ? i + kM : r > 3 ? i - (kN - kM) : (l < kN - kM - 192 ? i + kM : i - (kN - kM));
-      const uint32_t v = twist1(mt[i], mt[i + 1], mt[ci]);
-      mt[i] = v;
-      __asm__ volatile("" ::: "memory");
-    }
-    mt[kN + l] = twist1(mt[l], mt[l + 1], mt[l + kM]);  // look-ahead: next block's words 0..63
-    __asm__ volatile("" ::: "memory");
-    mti -= kN;
-    wbase = -1024;
-    wend = 0;
-  }
-  __device__ void ensure() {
-    if (mti >= kN) twist();
-  }
-
-  __device__ void seed_i64(int64_t seed) {  // random.seed(int): init_by_array(abs(seed) limbs)
-    if (threadIdx.x == 0) {
-      const uint64_t a = seed < 0 ? (uint64_t)(-(seed + 1)) + 1 : (uint64_t)seed;
-      const uint32_t key[2] = {(uint32_t)a, (uint32_t)(a >> 32)};
-      const int klen = key[1] ? 2 : 1;
-      uint32_t prev = 19650218u;
-      mt[0] = prev;
-      for (int i = 1; i < kN; ++i) {
-        prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-        mt[i] = prev;
-      }
-      int i = 1, j = 0;
-      prev = mt[0];
-      for (int k = kN; k; --k) {
-        const uint32_t v = (mt[i] ^ ((prev ^ (prev >> 30)) * 1664525u)) + key[j] + (uint32_t)j;
-        mt[i] = v;
-        prev = v;
-        ++i;
-        ++j;
-        if (i >= kN) { mt[0] = mt[kN - 1]; prev = mt[0]; i = 1; }
-        if (j >= klen) j = 0;
-      }
-      for (int k = kN - 1; k; --k) {
-        const uint32_t v = (mt[i] ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (uint32_t)i;
-        mt[i] = v;
-        prev = v;
-        ++i;
-        if (i >= kN) { mt[0] = mt[kN - 1]; prev = mt[0]; i = 1; }
-      }
-      mt[0] = 0x80000000u;
-      mt[kN] = twist1(mt[0], mt[1], mt[kM]);  // look-ahead word 0 (= the first twist's new[0])
-    }
-    __syncthreads();
-    mti = kN;  // CPython leaves index = N after seeding: the first draw twists
-    wbase = -1024;
-    wend = 0;
-  }
-
-  // out of line: runs once per 64 draws (window load) or per 624 draws (twist)
-  __device__ void refill() {
-    ensure();
-    wbase = mti;
-    wend = mti + 64;
-    win = temper(mt[mti + (int)threadIdx.x]);
-  }
-  __device__ uint32_t u32() {
-    if (mti >= wend) refill();  // one scalar compare per draw
-    const uint32_t v = rdlane(win, mti - wbase);
-    mti = uni(mti + 1);
-    return v;
-  }
-  // Fisher-Yates draws of random.shuffle over n items: j_i = _randbelow(i+1), i = n-1 .. 1,
-  // delivered as sink(off, j) by every lane of every window: off = i for the lane whose word
-  // is drawn for step i and accepted, 0 for every other lane (rejected words, words past the
-  // end; index 0 of a draw array is never read, so the sink stores unconditionally - no
-  // exec-mask branch per window). Wave-parallel over a window of 64 words (lane t holds word t).
-  // Word t of the window is drawn for step i_t = s0 - t + R_t (R_t = rejections before t) and
-  // rejected iff (w_t >> (32 - bit_length(i_t + 1))) > i_t, i.e. with u = i + 1 (the draw's
-  // bound) iff (w_t >> clz(u)) >= u. R is the fixed point of R_t = #{v < t : rejected under
-  // R_v}, found by Jacobi iteration on ballots: the recurrence is causal, so every pass fixes at
-  // least the first wrong word. Words past the last step (u <= 1) come after every valid word
-  // and do not affect their R; they are held "accepted" (a verdict that followed their R would
-  // keep changing and cost passes: 11.7 instead of ~5 per window), and the first of them ends
-  // the shuffle. The window's bookkeeping is branch-free scalar work (s_ff1 / s_bcnt1).
-  template <typename Sink>
-  __device__ void fy_draws(int32_t n, Sink sink) {
-    const int lane = threadIdx.x;
-    int32_t s0 = n - 1;  // next step (uniform); n < 2^30 (host-checked)
-    while (s0 >= 1) {
-      ensure();
-      const uint32_t w = temper(mt[mti + lane]);
-      const int32_t u1 = s0 + 1 - lane;
-      // Jacobi start: ~0.3 rejections per word (any start converges to the same fixed point,
-      // the left-most wrong word being fixed by every pass; simulated: 5.3 -> 4.8 passes per
-      // window at target_seq_length 128)
-      int32_t R = (lane * 77) >> 8;
-      uint32_t x;
-      uint64_t rej;
-      // Convergence is tested on the rejection masks (one scalar 64-bit compare): from the second
-      // pass on, R = popc_below(previous mask), so equal masks give equal R in every lane (bit 63
-      // moves no R: at most one extra pass). The loop carries no vector compare and no R copy.
-      if (s0 >= 64) {  // every word of the window has a step (u >= 2)
-        auto pass = [&]() {
-          const int32_t u = u1 + R;
-          x = w >> __clz((uint32_t)u);
-#ifdef LDDL_STAMPS
-          ++n_pass;
-#endif
-          return ballot(x >= (uint32_t)u);
-        };
-        uint64_t prev = pass();
-        R = (int32_t)popc_below(prev);
-        rej = pass();
-        while (rej != prev) {
-          prev = rej;
-          R = (int32_t)popc_below(rej);
-          rej = pass();
-        }
-      } else {  // words past the last step (u <= 1) are held "accepted", so they settle at once
-        auto pass = [&]() {
-          const int32_t u = u1 + R;
-          x = w >> (__clz((uint32_t)u) & 31);
-#ifdef LDDL_STAMPS
-          ++n_pass;
-#endif
-          return ballot(x >= (uint32_t)u) & ballot(u > 1);
-        };
-        uint64_t prev = pass();
-        R = (int32_t)popc_below(prev);
-        rej = pass();
-        while (rej != prev) {
-          prev = rej;
-          R = (int32_t)popc_below(rej);
-          rej = pass();
-        }
-      }
-#ifdef LDDL_STAMPS
-      ++n_win;
-#endif
-      const int32_t i = u1 + R - 1;  // the lane's step (<= 0 past the end)
-      // (the verdict is recomputed here rather than carried out of the loop as a lane mask)
-      sink(x > (uint32_t)i ? 0 : max(i, 0), x);
-      // the shuffle ends at the first word past the last step (E); words < E are consumed. After
-      // such a window s0 - (64 - popc(rej)) <= 0, since the held words count as accepted.
-      const uint64_t fin = ballot(i < 1);
-      mti = uni(mti + (fin ? (int)__ffsll((unsigned long long)fin) - 1 : 64));
-      s0 -= 64 - (int32_t)__popcll(rej);
-    }
-    wbase = -1024;
-    wend = 0;  // the register window is stale
-  }
-  // _truncate_seq_pair draws (pretrain.py:161-176). T = na + nb - max_num trims; trim t hits A
-  // iff A is the longer side at that point, which has a closed form: with d = na - nb the first
-  // |d| trims hit the longer side, then B and A alternate starting with B (ties trim B). Each
-  // trim is from the front iff random() < 0.5, i.e. iff the first of its two words is < 2^31, so
-  // 32 trims (64 words, the look-ahead) resolve per wave pass with two ballots.
-  __device__ void trunc_draws(int32_t& na, int32_t& nb, int32_t max_num, int32_t& a_front,
-                              int32_t& b_front) {
-    const int32_t T = na + nb - max_num;
-    if (T <= 0) return;
-    const int32_t d = na - nb, ad = d < 0 ? -d : d;
-    const int lane = threadIdx.x;
-    for (int32_t done = 0; done < T;) {
-      ensure();
-      const int32_t cnt = min(T - done, 32);
-      const int32_t t = done + lane;
-      // random() < 0.5 <=> the tempered first word's top bit is clear; tempering is linear over
-      // GF(2) and that bit is the parity of raw bits 31, 27, 24 and 16
-      // (every lane reads: mti + 126 stays inside the LDS block; lanes >= cnt are masked off
-      // by the scalar lane mask, not by an exec-mask branch)
-      const uint32_t par = __popc(mt[mti + 2 * lane] & 0x89010000u) & 1u;
-      const uint64_t F = ballot(par == 0) & ((1ull << cnt) - 1);  // cnt <= 32
-      const int32_t x = t - ad;
-      const uint64_t S = ballot(t < d) | (ballot(x >= 0) & ballot((x & 1) != 0));
-      a_front += __popcll(F & S);
-      b_front += __popcll(F & ~S);
-      mti = uni(mti + 2 * cnt);
-      done += cnt;
-    }
-    wbase = -1024;
-    wend = 0;
-    const int32_t nA = (d > 0 ? min(d, T) : 0) + (T > ad ? (T - ad) / 2 : 0);
-    na -= nA;
-    nb -= T - nA;
-  }
-
-  // Decisions of create_masked_lm_predictions (pretrain.py:208-221) for cnt masked tokens:
-  // random() < 0.8 -> [MASK]; else random() < 0.5 -> keep; else vocab_words[randint(0, V-1)].
-  // Lane t tabulates the decision and word count of a token whose first word is mti + t (only
-  // decisions whose words lie in the 64-word look-ahead); the chain of decision starts p_0 = 0,
-  // p_{k+1} = p_k + len[p_k] is then resolved for every k at once by pointer doubling
-  // (ds_bpermute), so lane k learns where decision k starts (a window holds <= 32 decisions).
-  // cnt <= 64; returns decision `lane` in each lane < cnt.
-  __device__ int32_t mask_decisions(int cnt, uint64_t lt08, int32_t V, int32_t mask_id) {
-    const int lane = threadIdx.x;
-    const int kV = 32 - __clz((uint32_t)V);
-    int32_t res = 0;
-    int c = 0;
-    while (c < cnt) {
-      ensure();
-      // word t + j of the window reaches lane t by j whole-wave DPP shifts (one LDS read and one
-      // temper per lane); only words inside the look-ahead are used
-      const uint32_t* wp = mt + mti + lane;
-      const uint32_t w0 = temper(wp[0]);
-      const uint32_t w1 = (uint32_t)wave_next((int)w0), w2 = (uint32_t)wave_next((int)w1),
-                     w3 = (uint32_t)wave_next((int)w2), w4 = (uint32_t)wave_next((int)w3);
-      (void)w3;
-      // random() < 0.8 <=> N = (w0 >> 5) * 2^26 + (w1 >> 6) < lt08 <=> (w0 >> 5) * 2^32 + w1 <
-      // lt08 * 64 (w1's low 6 bits cannot carry past a multiple of 64): one shift, one compare
-      const uint64_t N64 = ((uint64_t)(w0 >> 5) << 32) | w1;
-      // the decision at word t: [MASK] (2 words), else keep (random() < 0.5: w2's top bit clear,
-      // 4 words), else a random word (randint's first word w4 accepted: 5 words; rejected: the
-      // rare scan below); len 0 when the decision's words run past the look-ahead. Written as
-      // selects on three compares and a shift, so that no lane-mask logic runs on the scalar unit.
-      const bool mk = N64 < (lt08 << 6);
-      const uint32_t top = w2 >> 31;  // 1: not keep
-      const uint32_t r4 = w4 >> (32 - kV);
-      const bool r4ok = r4 < (uint32_t)V;
-      const int need = mk ? 2 : 4 + (int)top;
-      int len = lane + need > kLook ? 0 : mk ? 2 : top ? (r4ok ? 5 : 0) : 4;
-      int32_t tok = mk ? mask_id : top ? (int32_t)r4 : kKeep;
-      if (!mk && top && !r4ok) {  // randint rejected its first word: scan on (rare)
-        for (int j = 5; lane + j < kLook; ++j) {
-          const uint32_t r = temper(wp[j]) >> (32 - kV);
-          if (r < (uint32_t)V) {
-            len = j + 1;
-            tok = (int32_t)r;
-            break;
-          }
-        }
-      }
-      // J_b[t] = start after 2^b decisions from t (64: stop, absorbing)
-      int Jd[5];
-      Jd[0] = len ? min(lane + len, 64) : 64;
-#pragma unroll
-      for (int b = 1; b < 5; ++b) {
-        const int y = __shfl(Jd[b - 1], Jd[b - 1] & 63, 64);
-        Jd[b] = Jd[b - 1] >= 64 ? 64 : y;
-      }
-      int p = 0;  // start of decision `lane` (lanes < 32)
-#pragma unroll
-      for (int b = 0; b < 5; ++b) {
-        const int t = __shfl(Jd[b], p & 63, 64);
-        if ((lane >> b) & 1) p = p >= 64 ? 64 : t;
-      }
-      const int lp = __shfl(len, p & 63, 64);
-      const int32_t tp = __shfl(tok, p & 63, 64);
-      // a prefix of the lanes (two compares, the scalar unit ANDs their ballots)
-      const uint64_t okm = ballot(p < 64) & ballot(lp > 0) & 0xFFFFFFFFull;
-      int take = __ffsll((unsigned long long)~okm) - 1;
-      if (take > cnt - c) take = cnt - c;
-      const int32_t tk = __shfl(tp, (lane - c) & 63, 64);  // decision k goes to lane c + k
-      if (lane >= c && lane < c + take) res = tk;
-      if (take > 0) {
-        mti = uni(mti + (int)rdlane((uint32_t)p, take - 1) + (int)rdlane((uint32_t)lp, take - 1));
-        c += take;
-      } else {  // the first decision needs words past the look-ahead: draw it word by word
-        wbase = -1024;
-        wend = 0;
-        int32_t t2;
-        if (rand53() < lt08) t2 = mask_id;
-        else if (below_half()) t2 = kKeep;
-        else t2 = (int32_t)randint(0, V - 1);
-        if (lane == c) res = t2;
-        ++c;
-      }
-    }
-    wbase = -1024;
-    wend = 0;
-    return res;
-  }
-
-  // random() = N / 2^53 with N = (w1 >> 5) * 2^26 + (w2 >> 6). `random() < p` is decided exactly
-  // on N: N < ceil(p * 2^53) (see k_short / kLt08), so no floating point is needed.
-  // two consecutive words with one window check when both are in the window
-  __device__ void u32x2(uint32_t& a, uint32_t& b) {
-    if (mti + 1 < wend) {
-      a = rdlane(win, mti - wbase);
-      b = rdlane(win, mti + 1 - wbase);
-      mti = uni(mti + 2);
-    } else {
-      a = u32();
-      b = u32();
-    }
-  }
-  __device__ uint64_t rand53() {
-    uint32_t a, b;
-    u32x2(a, b);
-    return ((uint64_t)(a >> 5) << 26) | (b >> 6);
-  }
-  __device__ bool below_half() {  // random() < 0.5  <=>  N < 2^52  <=>  w1 < 2^31
-    uint32_t a, b;
-    u32x2(a, b);
-    return a < 0x80000000u;
-  }
-  __device__ uint32_t randbelow(uint32_t n) {
-    const int k = 32 - __clz(n);
-    uint32_t r = u32() >> (32 - k);
-    while (r >= n) r = u32() >> (32 - k);
-    return r;
-  }
-  __device__ int64_t randint(int64_t a, int64_t b) { return a + randbelow((uint32_t)(b - a + 1)); }
-  __device__ int32_t randint32(int32_t a, int32_t b) { return a + (int32_t)randbelow((uint32_t)(b - a + 1)); }
-
-};
-
-constexpr int kDocLds = 512;  // partitions with <= this many documents cache offsets in LDS
 constexpr uint64_t kLt08 = 7205759403792794ull;  // ceil(0.8 (binary64) * 2^53): random() < 0.8
-
-// Sentence lengths of one document through a 64-entry register window (lane l: sentence
-// wbase + l) with their inclusive prefix sum, so a chunk end is one ballot and a span's length
-// two readlanes. Lengths are < 2^24 (lddl_tokenize caps max_pieces), so 64 of them fit int32.
-struct LenWin {
-  const int32_t* len;  // ks_len + first kept sentence of the doc
-  int n, wbase;
-  int32_t win, pre;
-  uint64_t fl;  // lanes whose sentence holds a literal [CLS]/[SEP]
-  __device__ void reset(const int32_t* p, int nn) { len = p; n = nn; wbase = -1024; }
-  // the first window of a document loaded ahead (issued one document early, so the chain does not
-  // wait for it), then taken as the window at sentence 0
-  int32_t pfw;
-  __device__ void prefetch(const int32_t* p, int nn) {
-    const int k = (int)threadIdx.x;
-    pfw = k < nn ? p[k] : 0;
-  }
-  __device__ void reset_prefetched(const int32_t* p, int nn) {
-    len = p;
-    n = nn;
-    wbase = 0;
-    win = pfw;
-    pre = wave_incl_scan(win & kLenMask);
-    fl = ballot((win & kLenHasClsSep) != 0);
-  }
-  __device__ bool has(int j) const { return (unsigned)(j - wbase) < 64u; }  // (j >= 0)
-  __device__ void load(int j) {
-    wbase = j;
-    const int k = j + (int)threadIdx.x;
-    win = k < n ? len[k] : 0;
-    pre = wave_incl_scan(win & kLenMask);
-    fl = ballot((win & kLenHasClsSep) != 0);
-  }
-  __device__ int32_t at(int j) {  // raw length word (flags included)
-    if (!has(j)) load(j);
-    return (int32_t)rdlane((uint32_t)win, j - wbase);
-  }
-  // total length of sentences [a, b) (a < b); ORs their flags into `flags`
-  __device__ int64_t sum(int a, int b, int32_t& flags) {
-    if (!has(a)) load(a);
-    if (!has(b - 1)) {  // longer than a window: sequential
-      int64_t s = 0;
-      for (int j = a; j < b; ++j) {
-        const int32_t w = at(j);
-        s += w & kLenMask;
-        flags |= w;
-      }
-      return s;
-    }
-    const int32_t hi = (int32_t)rdlane((uint32_t)pre, b - 1 - wbase);
-    const int32_t lo = a > wbase ? (int32_t)rdlane((uint32_t)pre, a - 1 - wbase) : 0;
-    if (fl) {  // (a window without literal [CLS]/[SEP] skips the span mask: the common case)
-      const int cnt = b - a;
-      const uint64_t m = fl >> (a - wbase);
-      if ((cnt >= 64 ? m : (m & ((1ull << cnt) - 1))) != 0) flags |= kLenHasClsSep;
-    }
-    return hi - lo;
-  }
-  // the smallest i in [a, lim) with length(a .. i) >= T, else lim - 1 (a < lim <= n): the end of
-  // the reference's accumulate-until-target loops (pretrain.py:276-280, 314-317)
-  __device__ int find(int a, int lim, int64_t T) {
-    if (!has(a)) load(a);
-    // (window sums are < 2^31: 32-bit compares; two ballots combined by one scalar AND)
-    const int32_t T32 = T < -1 ? -1 : T > INT32_MAX ? INT32_MAX : (int32_t)T;
-    for (int pass = 0; pass < 2; ++pass) {
-      const int32_t base = a > wbase ? (int32_t)rdlane((uint32_t)pre, a - 1 - wbase) : 0;
-      const int j = wbase + (int)threadIdx.x;
-      const uint64_t m = ballot((uint32_t)(j - a) < (uint32_t)(lim - a)) & ballot(pre - base >= T32);
-      if (m) return wbase + __ffsll((unsigned long long)m) - 1;
-      if (wbase + 64 >= lim) return lim - 1;
-      if (pass == 0 && wbase != a) load(a);  // restart the window at a and look again
-      else break;
-    }
-    int64_t s = 0;  // more than 64 sentences: sequential
-    for (int i = a;; ++i) {
-      s += at(i) & kLenMask;
-      if (i == lim - 1 || s >= T) return i;
-    }
-  }
-};
-
-// token j (0-based) of the span that starts at kept sentence k0 (slow path only: a literal
-// [CLS]/[SEP] in the pair), read from the tokenizer's layout
-__device__ int32_t span_token(const PlanArgs& A, int64_t k0, int64_t j) {
-  const int64_t x = A.kscan[k0] + j;
-  int64_t k = k0;
-  while (A.kscan[k + 1] <= x) ++k;
-  return A.ids[A.ks_start[k] + (x - A.kscan[k])];
-}
-
-// Kept tokens packed densely (see densify_kernel below):
-// one wave: kept sentences [k0, k0 + 64)
-__device__ inline void densify_group(int64_t k0, const int64_t* __restrict__ ks_start,
-                                     const int32_t* __restrict__ ks_len,
-                                     const int64_t* __restrict__ kscan, int64_t n,
-                                     const int32_t* __restrict__ ids, IdPtr dense) {
-  const int lane = threadIdx.x & 63;
-  const int64_t k = k0 + lane;
-  const bool ok = k < n;
-  const int32_t len = ok ? ks_len[k] & kLenMask : 0;
-  const int64_t st = ok ? ks_start[k] : 0;
-  const int32_t incl = wave_incl_scan(len);
-  const int32_t total = __builtin_amdgcn_readlane(incl, 63);  // (uniform: scalar loop bounds)
-  const int64_t base = kscan[k0];
-  // the sentence loop indices are wave-uniform: lane values via readlane, not LDS permutes
-  auto rl = [](int32_t v, int i) { return __builtin_amdgcn_readlane(v, i); };
-  // kU chunks of 64 tokens per round: their sources first, then all kU loads, then the stores,
-  // so a wave has kU loads in flight instead of one dependent load -> store per chunk
-  constexpr int kU = 4;  // (8: 6.0 -> 6.3 ms, profiles/r06y)
-  int j = 0;
-  for (int32_t c0 = 0; c0 < total; c0 += 64 * kU) {
-    int64_t src[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int32_t cu = c0 + 64 * u, x = cu + lane, hi = min(cu + 63, total - 1);
-      src[u] = 0;
-      if (cu < total) {
-        while (rl(incl, j) <= cu) ++j;  // first sentence overlapping the chunk
-        for (int jj = j;; ++jj) {
-          const int32_t e = rl(incl, jj);
-          const int32_t b = e - rl(len, jj);
-          const int64_t s = ((int64_t)rl((int32_t)(st >> 32), jj) << 32) | (uint32_t)rl((int32_t)st, jj);
-          if (x >= b && x < e) src[u] = s + (x - b);
-          if (e > hi) break;
-        }
-      }
-    }
-    int32_t v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) v[u] = c0 + 64 * u + lane < total ? ids[src[u]] : 0;
-#pragma unroll
-    for (int u = 0; u < kU; ++u)
-      if (c0 + 64 * u + lane < total) dense.st(base + c0 + 64 * u + lane, v[u]);
-  }
-}
 
 // waves per SIMD the compiler must keep: 8 caps the kernel at 78 SGPRs (140 spilled to VGPR
 // lanes); 6 lets it use all 106 (59 spilled) at 7 waves/SIMD, 176 -> 169.6 ms per 10 GB
 // (profiles/r02_plan_minw_ab.txt)
 // kDocsLds: every partition's document offsets fit the LDS table (host-checked: <= kDocLds
-// documents), so the document lookups carry no global-memory branch; kJB: bytes per shuffle draw
-//
-// The time-sliced mode (kSliced; a one-range plan of more partitions than the device holds
-// waves). The grid is persistent one-wave workgroups, as many as the device holds. A wave plans
-// a partition for a quantum of documents, parks it at the document boundary and takes the next
-// item of a global FIFO, so every partition gets slice k before any gets slice k + 1 and all
-// the chains end together, with every wave slot busy until then.
-//   Tickets, all claimed by a returning add on sl_ctl[0], the first one when the wave starts: a
-//   workgroup owns no work by its index, so one that becomes resident late (measured with the
-//   first tickets bound to the workgroup index: 1,024 of 7,168 started when the others left and
-//   planned their partitions alone, 152 ms) finds the queue as it then is. Ticket t < n_part is
-//   the fresh partition t (seeded as in the one-shot mode), ticket n_part + r is entry r of a
-//   ring that never wraps (the host sizes it from the quantum: plan_slice_ring_entries).
-//   Parking. The wave writes the partition's state (the MT block with its look-ahead, mti, the
-//   loop position, np and the partition's pool chunks: kSaveU64 granules) to the partition's save
-//   area with write-through agent-scope stores, drains them (s_waitcnt vmcnt(0)), reserves a ring
-//   index with one returning add on sl_ctl[1] and publishes partition + 1 there by an atomic
-//   exchange. Then it claims its next ticket.
-//   Claiming. The claimant of ring entry r exchanges kRingAbandoned into it. A partition id
-//   coming back is its work item: one agent-scope acquire, then the state is read by vector loads
-//   (lane-indexed addresses, through LDS; the uniform words become scalars by readfirstlane). Zero
-//   coming back (after kPopTries looks: the entry is reserved but not yet written, or the ring is
-//   empty) means the wave leaves the queue for good.
-//   No wave waits for another, and nothing is lost: the exchanges on one ring word are totally
-//   ordered, so either the claimant sees the partition id and owns the partition, or the
-//   publisher sees kRingAbandoned and keeps its partition for another slice (it alone ever held
-//   it). Every ticket below the final sl_ctl[0] has exactly one claimant, and the final count
-//   covers every published entry: each slice end (a parking that was not handed back, or a
-//   finished partition) is followed by one claim, which makes n_part + published - abandoned
-//   claims on top of the waves' first ones, and no more entries are ever abandoned than there are
-//   waves (a wave abandons one entry, then leaves). So no workgroup's progress depends on another
-//   being resident, and the launch ends whatever the dispatch order.
-//   The pool chunks belong to the partition here (parked with it), not to the wave: the pools'
-//   total use is then the same whichever wave plans which slice, which the exact-size re-plan
-//   after a pool overflow relies on.
-//   A wave that leaves the queue packs `dense`: groups of kept sentences claimed from sl_ctl[2].
-constexpr int kSaveHdr = 16;                            // header words behind the MT block
-constexpr int kSaveU64 = (kN + kLook + kSaveHdr) / 2;   // 8-byte granules per parked partition
-constexpr int kPopTries = 4;                            // looks at a ring entry that reads zero
-constexpr unsigned kRingAbandoned = 0xFFFFFFFFu;
-constexpr int kDenseClaim = 4;                          // 64-sentence groups per claim
-static_assert((kN + kLook + kSaveHdr) % 2 == 0 && kSaveHdr <= kDocLds, "save area layout");
-
-#define LDDL_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-// Claims the wave's next ticket (uniform): -1 = leave the queue, else the ticket, with *part the
-// partition to plan (fresh when ticket < n_part, else parked).
-__device__ inline int32_t slice_claim(const PlanArgs& A, int32_t* part) {
-  int32_t t_out = -1, p_out = 0;
-  if (threadIdx.x == 0) {
-    const unsigned t = __hip_atomic_fetch_add(&A.sl_ctl[0], 1u, LDDL_RLX_AGENT);
-    if (t < (unsigned)A.n_part) {
-      t_out = (int32_t)t;
-      p_out = (int32_t)t;
-    } else if (t - (unsigned)A.n_part < (unsigned)A.sl_ring_cap) {
-      unsigned* e = A.sl_ring + (t - (unsigned)A.n_part);
-      for (int tries = 1; tries < kPopTries; ++tries) {  // (bounded: then the exchange decides)
-        if (__hip_atomic_load(e, LDDL_RLX_AGENT) != 0) break;
-        __builtin_amdgcn_s_sleep(4);
-      }
-      const unsigned v = __hip_atomic_exchange(e, kRingAbandoned, LDDL_RLX_AGENT);
-      if (v != 0 && v != kRingAbandoned) {
-        t_out = (int32_t)t;
-        p_out = (int32_t)(v - 1);
-      }
-    }
-  }
-  *part = uni(p_out);
-  return uni(t_out);
-}
-
-// Publishes the parked partition p (its state is stored and drained). true: handed on; false: the
-// entry had been abandoned (or the ring is full), the wave keeps the partition.
-__device__ inline bool slice_publish(const PlanArgs& A, int32_t p) {
-  int32_t on = 0;
-  if (threadIdx.x == 0) {
-    const unsigned r = __hip_atomic_fetch_add(&A.sl_ctl[1], 1u, LDDL_RLX_AGENT);
-    if (r < (unsigned)A.sl_ring_cap)
-      on = __hip_atomic_exchange(A.sl_ring + r, (unsigned)p + 1u, LDDL_RLX_AGENT) == 0;
-  }
-  // the publish is complete before the wave's own claim reads the queue
-  __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  return uni(on) != 0;
-}
-
+// documents), so the document lookups carry no global-memory branch; kJB: bytes per shuffle draw;
+// kSliced: the time-sliced mode (replay_slice.h)
 template <bool kDocsLds, int kJB, bool kSliced = false>
 __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -648,16 +81,16 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
     uint64_t* s64 = reinterpret_cast<uint64_t*>(s_mt);
     for (int i = lane; i < kSaveU64; i += 64) s64[i] = sv[i];
     __syncthreads();
-    const int32_t* h = s_doc;  // the header words follow the MT block
-    rng.mti = uni(h[0]);
-    dp0 = uni(h[1]);
-    di0 = uni(h[2]);
-    np = ((int64_t)uni(h[11]) << 32) | (uint32_t)uni(h[3]);
-    pool_cur = ((int64_t)uni(h[5]) << 32) | (uint32_t)uni(h[4]);
-    pool_left = uni(h[6]);
-    jpool_cur = ((int64_t)uni(h[8]) << 32) | (uint32_t)uni(h[7]);
-    jpool_left = uni(h[9]);
-    const int32_t fb = uni(h[10]);
+    const int32_t* h = s_doc;  // the header words (ParkWord) follow the MT block
+    rng.mti = uni(h[kParkMti]);
+    dp0 = uni(h[kParkDp]);
+    di0 = uni(h[kParkDi]);
+    np = ((int64_t)uni(h[kParkNpHi]) << 32) | (uint32_t)uni(h[kParkNpLo]);
+    pool_cur = ((int64_t)uni(h[kParkPoolHi]) << 32) | (uint32_t)uni(h[kParkPoolLo]);
+    pool_left = uni(h[kParkPoolLeft]);
+    jpool_cur = ((int64_t)uni(h[kParkJpoolHi]) << 32) | (uint32_t)uni(h[kParkJpoolLo]);
+    jpool_left = uni(h[kParkJpoolLeft]);
+    const int32_t fb = uni(h[kParkFits]);
     pool_fits = (fb & 1) != 0;
     jpool_fits = (fb & 2) != 0;
     __syncthreads();  // (before the document table overwrites the header)
@@ -701,12 +134,21 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
           // The header words go behind the MT block in LDS (over the document table, which the
           // next slice loads again), then the block leaves as 8-byte write-through stores.
           int32_t hw = 0;
-          const int32_t hv[12] = {rng.mti, dp, di, (int32_t)np, (int32_t)pool_cur,
-                                  (int32_t)(pool_cur >> 32), pool_left, (int32_t)jpool_cur,
-                                  (int32_t)(jpool_cur >> 32), jpool_left,
-                                  (pool_fits ? 1 : 0) | (jpool_fits ? 2 : 0), (int32_t)(np >> 32)};
+          int32_t hv[kParkWords];
+          hv[kParkMti] = rng.mti;
+          hv[kParkDp] = dp;
+          hv[kParkDi] = di;
+          hv[kParkNpLo] = (int32_t)np;
+          hv[kParkPoolLo] = (int32_t)pool_cur;
+          hv[kParkPoolHi] = (int32_t)(pool_cur >> 32);
+          hv[kParkPoolLeft] = pool_left;
+          hv[kParkJpoolLo] = (int32_t)jpool_cur;
+          hv[kParkJpoolHi] = (int32_t)(jpool_cur >> 32);
+          hv[kParkJpoolLeft] = jpool_left;
+          hv[kParkFits] = (pool_fits ? 1 : 0) | (jpool_fits ? 2 : 0);
+          hv[kParkNpHi] = (int32_t)(np >> 32);
 #pragma unroll
-          for (int k = 0; k < 12; ++k)
+          for (int k = 0; k < kParkWords; ++k)
             if (lane == k) hw = hv[k];
           __syncthreads();
           if (lane < kSaveHdr) s_doc[lane] = hw;
@@ -842,18 +284,13 @@ __global__ void __launch_bounds__(64, 6) plan_replay_kernel(PlanArgs A) {
           // written here: fy_draws' lanes store their rejected words there, and fy_resolve
           // takes j_0 = 0 itself.)
           const int32_t ip = nc + lane;
-          if constexpr (kJB == 1) {
-            uint8_t* jd = static_cast<uint8_t*>(A.jpool) + jb;
+          {
+            using Draw = std::conditional_t<kJB == 1, uint8_t, uint16_t>;
+            Draw* jd = static_cast<Draw*>(A.jpool) + jb;
             rng.fy_draws(nc, [&](int32_t i, uint32_t j) {
-              if (fits) jd[i] = (uint8_t)j;  // (fits is uniform: a scalar branch)
+              if (fits) jd[i] = (Draw)j;  // (fits is uniform: a scalar branch)
             });
-            if (fits && ip < ((nc + 15) & ~15)) jd[ip] = (uint8_t)ip;
-          } else {
-            uint16_t* jd = static_cast<uint16_t*>(A.jpool) + jb;
-            rng.fy_draws(nc, [&](int32_t i, uint32_t j) {
-              if (fits) jd[i] = (uint16_t)j;
-            });
-            if (fits && ip < ((nc + 15) & ~15)) jd[ip] = (uint16_t)ip;
+            if (fits && ip < ((nc + 15) & ~15)) jd[ip] = (Draw)ip;
           }
           STAMP_ADD(2, st_t);
           // decisions of the masked candidates in shuffled order (pretrain.py:208-221)
@@ -951,21 +388,6 @@ struct Identity {
   __device__ int64_t operator()(int64_t i) const { return v[i]; }
 };
 
-// Kept tokens packed densely in kept-sentence order: kept sentence k's pieces are
-// dense[kscan[k] .. kscan[k+1]). A pair's A (and B) window is then one contiguous run
-// dense[kscan[a_ks] + a_front ..+ na), because a span only ever covers consecutive kept
-// sentences of one document. One wave per 64 kept sentences; 64-token output chunks are stored
-// coalesced, each lane finding its sentence among the few that overlap the chunk.
-__global__ void __launch_bounds__(256) densify_kernel(const int64_t* __restrict__ ks_start,
-                                                      const int32_t* __restrict__ ks_len,
-                                                      const int64_t* __restrict__ kscan, int64_t n,
-                                                      const int32_t* __restrict__ ids,
-                                                      IdPtr dense) {
-  const int64_t k0 = ((int64_t)blockIdx.x * 4 + wave_id()) * 64;
-  if (k0 >= n) return;
-  densify_group(k0, ks_start, ks_len, kscan, n, ids, dense);
-}
-
 // Split plan: the first kept sentence of the tail range's partitions (= the end of the head's)
 // and the kept tokens before it. info[0] bounds the two ranges' dense packing, info[1] scales
 // the head's counts to the suggested output capacities.
@@ -974,20 +396,6 @@ __global__ void split_info_kernel(const int64_t* kp_off, const int64_t* kd_off, 
   const int64_t k = kd_off[kp_off[s]];
   info[0] = k;
   info[1] = kscan[k];
-}
-
-// densify_kernel over kept sentences [0, *n_ptr): the head range of a split plan (the launch
-// covers all kept sentences; the workgroups past the bound leave at once)
-__global__ void __launch_bounds__(256) densify_head_kernel(const int64_t* __restrict__ ks_start,
-                                                           const int32_t* __restrict__ ks_len,
-                                                           const int64_t* __restrict__ kscan,
-                                                           const int64_t* __restrict__ n_ptr,
-                                                           const int32_t* __restrict__ ids,
-                                                           IdPtr dense) {
-  const int64_t n = *n_ptr;
-  const int64_t k0 = ((int64_t)blockIdx.x * 4 + wave_id()) * 64;
-  if (k0 >= n) return;
-  densify_group(k0, ks_start, ks_len, kscan, n, ids, dense);
 }
 
 // part_base[s + 1 + i] = head_pairs + rel[i + 1], i in [0, n): the tail range's partitions in
@@ -999,15 +407,6 @@ __global__ void tail_part_base_kernel(const int64_t* rel, int64_t n, int64_t hea
 }
 
 }  // namespace
-
-// densify_kernel over all kept sentences (n > 0), its one launch site: compact_inputs packs
-// `dense` with it when no planner launch does, launch_planner for a sliced plan that asks for it
-// (LDDL_PLAN_SLICE_DENSE)
-void launch_densify(const int64_t* ks_start, const int32_t* ks_len, const int64_t* kscan, int64_t n,
-                    const int32_t* ids, IdPtr dense, hipStream_t st) {
-  hipLaunchKernelGGL(densify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ks_start,
-                     ks_len, kscan, n, ids, dense);
-}
 
 // exclusive scan of v[0 .. n), out[n] = the total: scan_exclusive over Identity, instantiated here
 // alone (the planner's pairs per partition; the native planner's pairs per unit)
@@ -1078,7 +477,6 @@ static PlanKernel planner_kernel(const PlanWork& W, bool sliced) {
   return docs_lds ? (W.A.jbytes == 1 ? plan_replay_kernel<true, 1> : plan_replay_kernel<true, 2>)
                   : (W.A.jbytes == 1 ? plan_replay_kernel<false, 1> : plan_replay_kernel<false, 2>);
 }
-constexpr size_t kPlanLds = 4 * (kN + kLook) + 4 * (kDocLds + 4) + 16;  // ~4.8 KB: 7 waves/SIMD fit
 
 // The plan's mode (plan_replay_mode, plan_split.h: one shot, time-sliced or split at W.split.s)
 // and what follows from the decision to slice: the grid, the ring and the save areas.
@@ -1273,8 +671,7 @@ int plan_replay_split_head(lddl_pairs* P, PlanWork& W, bool* usable) {
   LDDL_HIP(hipEventRecord(P->ev_join, side));
   if (rc) return rc;
   if (P->n_kept_sent)
-    hipLaunchKernelGGL(densify_head_kernel, dim3((unsigned)((P->n_kept_sent + 255) / 256)), dim3(256),
-                       0, st, P->ks_start, P->ks_len, P->kscan, S.info, W.d_ids, P->dense);
+    launch_densify_head(P->ks_start, P->ks_len, P->kscan, P->n_kept_sent, S.info, W.d_ids, P->dense, st);
   unsigned long long ctl[4];
   if ((rc = read_back_range(W, 0, s, P->part_base, &P->rg[0].n_pairs, ctl, S.h_info, S.info, 16))) return rc;
   P->rg[0].p1 = s;

@@ -6,9 +6,18 @@
 //   pair_knobs.h       every environment knob of a plan, read when it starts (host-only)
 //   plan_split.h       the replay plan's host decisions: its mode, the split point, the ring
 //   pairs_compact.hip  compaction of the tokenizer's output (compact_inputs)
-//   pairs.hip          the replay planner; its mode, an attempt's pools and a range's read-back (it
-//                      keeps the file, and with it the history of the code most changes touch)
-//   pairs_native.hip   the native planner and its mask kernels (plan_native)
+//   pairs.hip          the replay planner: plan_replay_kernel and its three small kernels; the plan's
+//                      mode, an attempt's pools and a range's read-back (it keeps the file, and
+//                      with it the history of the code most changes touch)
+//   replay_rng.h       its device pieces: CPython's MT19937 wave-uniform (WaveRng),
+//   replay_len.h         the sentence-length window (LenWin, span_token),
+//   replay_slice.h       the time-sliced queue: protocol, save area, claim and publish, kPlanLds
+//   densify_dev.h      one wave's share of the dense packing (the planner's dense workgroups too)
+//   pairs_densify.hip  the dense packing as launches of its own (launch_densify, launch_densify_head)
+//   pairs_native.hip   the native planner: the walk, the keyed order, plan_native
+//   pairs_native_mask.hip  its two mask kernels, plain and whole-word (launch_native_masks)
+//   native_dev.h       what the two share on the device: the Philox streams, NativeArgs
+//   native_shape.h     the native launches' LDS sizes, grids and blocks (host-only)
 //   pairs_shuffle.hip  the replay plan's partition shuffle (shuffle_partitions)
 //   pairs_layout.hip   gather records, output-order scans, mask replay (layout_*)
 //   pairs_gather.hip   the gather (emit_ranges)

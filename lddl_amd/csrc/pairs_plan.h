@@ -102,7 +102,7 @@ struct PlanArgs {
   int64_t* part_npairs;
   uint64_t* stamps;  // diagnostic build: [n_part][8]
   uint64_t* tl;      // diagnostic build: [n_part][2] s_memrealtime at start / end (100 MHz)
-  // time-sliced mode (plan_replay_kernel<.., true>; see "The time-sliced mode", pairs.hip)
+  // time-sliced mode (plan_replay_kernel<.., true>; see "The time-sliced mode", replay_slice.h)
   unsigned* sl_ctl;   // [0] tickets claimed, [1] ring entries reserved (= hand-offs),
                       // [2] dense groups claimed, [3] unused; zeroed with the ring on every launch
   unsigned* sl_ring;  // [sl_ring_cap] 0 = not published, partition + 1, or kRingAbandoned
@@ -305,11 +305,14 @@ int tail_part_base(lddl_pairs* P, PlanWork& W);
 #ifdef LDDL_STAMPS
 int report_plan_stamps(const PlanWork& W);
 #endif
-// two kernels of pairs.hip have a caller in another unit; each has its one definition and
-// its one launcher there (no kernel symbol is shared between code objects)
+// the scan over Identity (pairs.hip) has a caller in another unit; it has its one instantiation
+// and its one launcher there (no kernel symbol is shared between code objects)
+hipError_t scan_i64(const int64_t* v, int64_t n, int64_t* out, int64_t* scratch, hipStream_t st);
+// pairs_densify.hip: the dense packing where no planner launch does it
 void launch_densify(const int64_t* ks_start, const int32_t* ks_len, const int64_t* kscan, int64_t n,
                     const int32_t* ids, IdPtr dense, hipStream_t st);
-hipError_t scan_i64(const int64_t* v, int64_t n, int64_t* out, int64_t* scratch, hipStream_t st);
+void launch_densify_head(const int64_t* ks_start, const int32_t* ks_len, const int64_t* kscan, int64_t n,
+                         const int64_t* n_ptr, const int32_t* ids, IdPtr dense, hipStream_t st);
 // pairs_shuffle.hip
 int shuffle_partitions(lddl_pairs* P, PlanWork& W, const PairRange& r, const int64_t* rel_base);
 // pairs_layout.hip

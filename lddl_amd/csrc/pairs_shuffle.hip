@@ -193,7 +193,7 @@ int shuffle_partitions(lddl_pairs* P, PlanWork& W, const PairRange& r, const int
     // gfx950), minus headroom for the kernel's static LDS
     const size_t kLdsBudget = std::min<size_t>(150 * 1024, W.c->lds_per_block > 10 * 1024
                                                                ? W.c->lds_per_block - 10 * 1024 : 0);
-    const bool force_global = getenv("LDDL_SHUFFLE_GLOBAL") != nullptr;  // tests: the large-partition path
+    const bool force_global = W.knobs.shuffle_global;  // LDDL_SHUFFLE_GLOBAL, tests: the large-partition path
     // partitions of <= cap_lds pairs: the parallel bucket-sort resolve (three 16-bit LDS tables);
     // larger ones: one lane swapping in global memory
     const int64_t cap_lds = force_global ? 0 : std::min<int64_t>({cap, 65534, (int64_t)(kLdsBudget / 6) - 2});

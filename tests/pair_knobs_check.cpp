@@ -24,13 +24,16 @@ using lddl::read_plan_knobs;
   } while (0)
 
 static const char* const kAll[] = {"LDDL_PLAN_SPLIT", "LDDL_PLAN_SLICE", "LDDL_PLAN_WAVES",
-                                   "LDDL_PLAN_SLICE_DENSE", "LDDL_AMD_MASK_POOL", "LDDL_FY_MODE",
-                                   "LDDL_FY_LW", "LDDL_FY_RA", "LDDL_FY_PF"};
+                                   "LDDL_PLAN_SLICE_DENSE", "LDDL_AMD_MASK_POOL", "LDDL_NATIVE_LDS_WORDS",
+                                   "LDDL_SHUFFLE_GLOBAL", "LDDL_FY_MODE", "LDDL_FY_LW", "LDDL_FY_RA",
+                                   "LDDL_FY_PF"};
 
 struct Knobs {
   int rc;
   FyKnobs fy;
   int64_t split, slice, waves, dense, pool;
+  int64_t lds_words;
+  bool shuffle_global;
 };
 
 // the knobs as a plan would read them with the environment {name = value, ...} (null: unset)
@@ -41,10 +44,12 @@ static Knobs read_with(const char* n0, const char* v0, const char* n1 = nullptr,
   if (n1 && v1) setenv(n1, v1, 1);
   if (n2 && v2) setenv(n2, v2, 1);
   PlanKnobs p;
-  p.split = p.slice = p.waves = p.slice_dense = p.mask_pool = 99;
+  p.split = p.slice = p.waves = p.slice_dense = p.mask_pool = p.native_lds_words = 99;
+  p.shuffle_global = true;
   p.fy = FyKnobs{99, 99, 99, 99};
   const int rc = read_plan_knobs(&p);
-  return Knobs{rc, p.fy, p.split, p.slice, p.waves, p.slice_dense, p.mask_pool};
+  return Knobs{rc, p.fy, p.split, p.slice, p.waves, p.slice_dense, p.mask_pool, p.native_lds_words,
+               p.shuffle_global};
 }
 
 static bool rejected(const Knobs& k, const char* msg) {
@@ -56,6 +61,7 @@ static const char kSliceMsg[] = "LDDL_PLAN_SLICE must be -1 (auto), 0 or a quant
 static const char kWavesMsg[] = "LDDL_PLAN_WAVES must be -1 (auto) or a workgroup count up to 2^20";
 static const char kDenseMsg[] = "LDDL_PLAN_SLICE_DENSE must be 0, 1 or 2";
 static const char kPoolMsg[] = "LDDL_AMD_MASK_POOL must be an entry count >= 0";
+static const char kLdsWordsMsg[] = "LDDL_NATIVE_LDS_WORDS must be a word count >= 0";
 static const char kBothMsg[] = "LDDL_PLAN_SPLIT and LDDL_PLAN_SLICE are both forced: a split plan is not sliced";
 static const char kRaPfMsg[] =
     "LDDL_FY_RA / PF select 16-lane branch-free variants (not with LDDL_FY_MODE=0 or LDDL_FY_LW=32)";
@@ -67,6 +73,7 @@ int main() {
     EXPECT(k.rc == 0 && k.split == -1 && k.slice == -1 && k.waves == -1);
     EXPECT(k.fy.mode == -1 && k.fy.lw == 16 && k.fy.ra == 1 && k.fy.pf == 4);
     EXPECT(k.dense == 1 && k.pool == -1);  // the waves that leave the queue; the pool sized by the plan
+    EXPECT(k.lds_words == -1 && !k.shuffle_global);  // the default cap; the shuffle's path by size
   }
   // ---- LDDL_PLAN_SPLIT and LDDL_PLAN_SLICE: -1, 0 or a count; a whole decimal number ----
   const struct {
@@ -118,6 +125,36 @@ int main() {
   EXPECT(rejected(read_with("LDDL_FY_MODE", "2", "LDDL_AMD_MASK_POOL", "-5"), kPoolMsg));
   // (and, malformed, before the conflict of the two forced knobs)
   EXPECT(rejected(read_with("LDDL_PLAN_SPLIT", "2", "LDDL_PLAN_SLICE", "3", "LDDL_AMD_MASK_POOL", ""), kPoolMsg));
+  // ---- LDDL_NATIVE_LDS_WORDS: a word count >= 0 (text used to read as 0) ----
+  for (int64_t v : {int64_t(0), int64_t(64), int64_t(24576), int64_t(1) << 40}) {
+    char text[32];
+    snprintf(text, sizeof text, "%lld", (long long)v);
+    const Knobs k = read_with("LDDL_NATIVE_LDS_WORDS", text);
+    EXPECT(k.rc == 0 && k.lds_words == v && !k.shuffle_global);
+    EXPECT(k.pool == -1 && k.dense == 1 && k.split == -1 && k.slice == -1 && k.waves == -1);
+  }
+  for (const char* bad : {"x", "", "-1", "-5", "64x", "6 4"})
+    EXPECT(rejected(read_with("LDDL_NATIVE_LDS_WORDS", bad), kLdsWordsMsg));
+  // (its message comes after LDDL_AMD_MASK_POOL's, before LDDL_FY_*' and before the conflict)
+  EXPECT(rejected(read_with("LDDL_NATIVE_LDS_WORDS", "x", "LDDL_AMD_MASK_POOL", "x"), kPoolMsg));
+  EXPECT(rejected(read_with("LDDL_NATIVE_LDS_WORDS", "x", "LDDL_PLAN_SPLIT", "x"), kSplitMsg));
+  EXPECT(rejected(read_with("LDDL_FY_MODE", "2", "LDDL_NATIVE_LDS_WORDS", "-1"), kLdsWordsMsg));
+  EXPECT(rejected(read_with("LDDL_PLAN_SPLIT", "2", "LDDL_PLAN_SLICE", "3", "LDDL_NATIVE_LDS_WORDS", "x"),
+                  kLdsWordsMsg));
+  // ---- LDDL_SHUFFLE_GLOBAL: set at all means forced, and nothing is refused ----
+  for (const char* any : {"1", "0", "", "x"}) {
+    const Knobs k = read_with("LDDL_SHUFFLE_GLOBAL", any);
+    EXPECT(k.rc == 0 && k.shuffle_global && k.lds_words == -1 && k.pool == -1 && k.dense == 1);
+    EXPECT(k.split == -1 && k.slice == -1 && k.waves == -1 && k.fy.mode == -1);
+  }
+  {
+    const Knobs k = read_with("LDDL_SHUFFLE_GLOBAL", "1", "LDDL_NATIVE_LDS_WORDS", "64");
+    EXPECT(k.rc == 0 && k.shuffle_global && k.lds_words == 64);
+    // (it is read after the numbers and before LDDL_FY_*: their refusals stand beside it)
+    EXPECT(rejected(read_with("LDDL_SHUFFLE_GLOBAL", "1", "LDDL_NATIVE_LDS_WORDS", "x"), kLdsWordsMsg));
+    EXPECT(rejected(read_with("LDDL_SHUFFLE_GLOBAL", "1", "LDDL_FY_MODE", "2"),
+                    "LDDL_FY_MODE must be -1 (auto), 0 or 1"));
+  }
   // ---- a forced split is not sliced; "one range" may be ----
   EXPECT(rejected(read_with("LDDL_PLAN_SPLIT", "2", "LDDL_PLAN_SLICE", "3"), kBothMsg));
   {
