@@ -23,30 +23,31 @@
 //   lddl_mask_dynamic_ww / lddl_collate_encode_masked_ww   the same two with whole-word masking
 //                         (DESIGN §15): a word = a head plus the continuation ("##x") ids behind
 //                         it, and the word's masked / not masked decision is its head's draw. One
-//                         wave per row, heads found by ballot; kernels of their own, the plain
-//                         ones are untouched.
+//                         wave per row, heads found by ballot; instantiations of their own, the
+//                         plain ones are untouched.
 //   lddl_mask_dynamic_span / lddl_collate_encode_masked_span   the same two with n-gram (span)
 //                         masking: whole words in runs of up to n, the run's reach
-//                         carried along the row as a wave prefix maximum (span_dev.h). Kernels
-//                         of their own again.
+//                         carried along the row as a wave prefix maximum (span_dev.h). The
+//                         whole-word kernels' other instantiation: one window loop per kernel,
+//                         the two modes apart in the one line of the decision.
 //
 // collate_dev.h holds what this unit shares with the other three collate units (the lookups, the
 // masking decision, the string-side arguments StrSample / StrLabels, SlotLayout for mask_special),
 // collate_host.h the host side of the entry points (the vocab check, the launch with its LDS
-// bound). encode_kernel owns its LDS staging, its two output loops and their predicates, written
-// out as in seqpack_kernel: collate_dev.h's comment at SlotLayout says why.
+// bound). encode_kernel owns its LDS staging, its two output loops (per token, and one for both
+// word modes) and their predicates, written out as in seqpack_kernel: collate_dev.h's comment at
+// SlotLayout says why.
 #include "collate_host.h"  // need_vocab, mask_draw_of, launch_rows; collate_dev.h
 #include "common.h"
 #include "ctx.h"
 #include "device.h"
 #include "lddl_amd.h"
 
-#include <type_traits>
-
 namespace lddl {
 namespace {
 
 struct EncodeArgs {
+  static constexpr int kMode = kPlain;
   StrSample S;
   int32_t B, L;
   int64_t* input_ids;
@@ -63,19 +64,26 @@ struct EncodeArgs {
 
 // One wave per sample; the row is staged in LDS (ids, labels as int32) in two barrier-separated
 // phases so that every output element is written exactly once, coalesced.
-// WW: the fused masking is whole-word and the arguments carry the continuation bitmap; the
-// plain instantiation is the kernel as it was, arguments and code.
-// SPAN (with WW): the fused masking is the n-gram one and the arguments carry its SpanDraw too.
+// The argument struct says the MODE (kMode), the enum of the other three collate kernels.
+// EncodeArgs, kPlain, is the kernel as it was, arguments and code: unmasked, static, and the
+// per-token fused masking too, which it takes from fused_mask at run time (there is no kFused
+// instantiation). EncodeWwArgs, kFusedWw: the fused masking is whole-word and the arguments carry
+// the continuation bitmap. EncodeSpanArgs, kFusedSpan: it is the n-gram one and they carry its
+// SpanDraw as well. (The kernel is a template over the struct and not over MODE with the struct
+// computed from it: a kernel's parameter type is part of its mangled name, and an expression
+// over the unnamed enum is spelled differently by the host and the device compilation, so that
+// the launch would not find the kernel.)
 struct EncodeWwArgs : EncodeArgs {
+  static constexpr int kMode = kFusedWw;
   ContBits cont;
 };
 struct EncodeSpanArgs : EncodeWwArgs {
+  static constexpr int kMode = kFusedSpan;
   SpanDraw span;
 };
-template <bool WW, bool SPAN = false>
-__global__ void __launch_bounds__(64 * kEncWaves)
-encode_kernel(std::conditional_t<SPAN, EncodeSpanArgs,
-                                 std::conditional_t<WW, EncodeWwArgs, EncodeArgs>> E) {
+template <typename Args>
+__global__ void __launch_bounds__(64 * kEncWaves) encode_kernel(Args E) {
+  constexpr int MODE = Args::kMode;
   extern __shared__ __attribute__((aligned(16))) int32_t srow[];
   const int w = wave_id(), lane = threadIdx.x & 63;
   const int b = blockIdx.x * kEncWaves + w;
@@ -117,10 +125,11 @@ encode_kernel(std::conditional_t<SPAN, EncodeSpanArgs,
   __syncthreads();
   if (!active) return;
   const int64_t row = (int64_t)b * E.L;
-  if constexpr (SPAN) {
-    // the whole-word windows below with span_masked for word_masked: every lane reaches its
-    // ballot and its scan
-    int32_t words_before = 0;
+  if constexpr (MODE == kFusedWw || MODE == kFusedSpan) {
+    // windows of 64 slots up to a multiple of 64, the tail predicated: every lane reaches the
+    // ballots (and with kFusedSpan the scan) of the word-unit step
+    bool carry = false;        // kFusedWw: the state of word_masked between the row's windows
+    int32_t words_before = 0;  // kFusedSpan: that of span_masked
     uint32_t carry_max = 0;
     for (int32_t x0 = 0; x0 < E.L; x0 += 64) {
       const int32_t x = x0 + lane;
@@ -130,30 +139,12 @@ encode_kernel(std::conditional_t<SPAN, EncodeSpanArgs,
       const int32_t id = in ? sid[x] : 0;
       const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
       const uint4 r = mask_draw(E.draw, row + x);
-      const bool m = span_masked(E.span, E.draw.counter, in && !special && !cont, r, row + x,
-                                 words_before, carry_max);
-      if (in) {
-        int64_t lab;
-        E.input_ids[row + x] = mask_apply(E.draw, r, !special && m, id, &lab);
-        E.labels[row + x] = lab;
-        E.token_type_ids[row + x] = (x >= na + 2 && x < end) ? 1 : 0;
-        E.attention_mask[row + x] = x < end ? 1 : 0;
-      }
-    }
-    return;
-  } else if constexpr (WW) {
-    // windows of 64 slots up to a multiple of 64, the tail predicated: every lane reaches the
-    // ballots of word_masked
-    bool carry = false;
-    for (int32_t x0 = 0; x0 < E.L; x0 += 64) {
-      const int32_t x = x0 + lane;
-      const bool in = x < E.L;
-      const bool special = x == 0 || x == na + 1 || x >= end - 1;
-      const bool prev_special = x <= 1 || x - 1 == na + 1 || x - 1 >= end - 1;  // of slot x - 1
-      const int32_t id = in ? sid[x] : 0;
-      const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
-      const uint4 r = mask_draw(E.draw, row + x);
-      const bool m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
+      bool m;  // the one line in which the two word modes differ
+      if constexpr (MODE == kFusedSpan)
+        m = span_masked(E.span, E.draw.counter, in && !special && !cont, r, row + x,
+                        words_before, carry_max);
+      else
+        m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
       if (in) {
         int64_t lab;
         E.input_ids[row + x] = mask_apply(E.draw, r, !special && m, id, &lab);
@@ -236,43 +227,20 @@ __global__ void __launch_bounds__(256) mask_kernel(MaskArgs M) {
 
 constexpr int kWwWaves = 4;
 
-// Whole-word lddl_mask_dynamic: one wave per row (a word never leaves its row), 64-slot windows.
-// The special flag of slot x - 1 comes from the lane below, across windows from lane 63.
-__global__ void __launch_bounds__(64 * kWwWaves) mask_ww_kernel(MaskArgs M, ContBits C) {
+// Whole-word (mask_words_kernel<kFusedWw>) and n-gram (<kFusedSpan, SpanDraw>) lddl_mask_dynamic:
+// one wave per row (a word never leaves its row), 64-slot windows. The special flag of slot x - 1
+// comes from the lane below, across windows from lane 63. Span is the n-gram kernel's third
+// argument, SpanDraw; the whole-word kernel has two, as it had. (A pack, not one body under two
+// __global__ functions: that form comes out with other code)
+template <int MODE, typename... Span>
+__global__ void __launch_bounds__(64 * kWwWaves) mask_words_kernel(MaskArgs M, ContBits C,
+                                                                   Span... S) {
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * kWwWaves + wave_id();
   if (b >= M.B) return;  // the whole wave
   const MaskDraw D{M.p, M.ignore_index, M.mask_id, M.vocab_len, M.seed, M.counter};
-  bool carry = false;
-  int last_special = 1;  // slot 0 has no slot before it: never a continuation
-  for (int64_t x0 = 0; x0 < M.L; x0 += 64) {
-    const int64_t x = x0 + lane, i = b * M.L + x;
-    const bool in = x < M.L;
-    const int64_t id = in ? M.ids[i] : 0;
-    const bool special = !in || mask_special(M, i, b, x, id);
-    const int up = __shfl_up((int)special, 1, 64);
-    const bool prev_special = lane == 0 ? last_special != 0 : up != 0;
-    last_special = __shfl((int)special, 63, 64);
-    const bool cont = !special && !prev_special && cont_id(C, id);
-    const uint4 r = mask_draw(D, i);
-    const bool m = word_masked(!cont, u01(r.x) < D.p, lane, carry);
-    if (in) {
-      int64_t lab;
-      const int64_t out = mask_apply(D, r, !special && m, id, &lab);
-      M.labels[i] = lab;
-      if (out != id) M.ids[i] = out;
-    }
-  }
-}
-
-// N-gram (span) lddl_mask_dynamic: mask_ww_kernel's rows and windows with the span decision.
-__global__ void __launch_bounds__(64 * kWwWaves) mask_span_kernel(MaskArgs M, ContBits C,
-                                                                  SpanDraw S) {
-  const int lane = threadIdx.x & 63;
-  const int64_t b = (int64_t)blockIdx.x * kWwWaves + wave_id();
-  if (b >= M.B) return;  // the whole wave
-  const MaskDraw D{M.p, M.ignore_index, M.mask_id, M.vocab_len, M.seed, M.counter};
-  int32_t words_before = 0;
+  bool carry = false;        // kFusedWw: the state of word_masked between the row's windows
+  int32_t words_before = 0;  // kFusedSpan: that of span_masked
   uint32_t carry_max = 0;
   int last_special = 1;  // slot 0 has no slot before it: never a continuation
   for (int64_t x0 = 0; x0 < M.L; x0 += 64) {
@@ -285,7 +253,11 @@ __global__ void __launch_bounds__(64 * kWwWaves) mask_span_kernel(MaskArgs M, Co
     last_special = __shfl((int)special, 63, 64);
     const bool cont = !special && !prev_special && cont_id(C, id);
     const uint4 r = mask_draw(D, i);
-    const bool m = span_masked(S, D.counter, !special && !cont, r, i, words_before, carry_max);
+    bool m;  // the one line in which the two word modes differ
+    if constexpr (MODE == kFusedSpan)
+      m = span_masked(S..., D.counter, !special && !cont, r, i, words_before, carry_max);
+    else
+      m = word_masked(!cont, u01(r.x) < D.p, lane, carry);
     if (in) {
       int64_t lab;
       const int64_t out = mask_apply(D, r, !special && m, id, &lab);
@@ -314,7 +286,7 @@ static int collate_encode(lddl_ctx* c, void* stream, const uint8_t* d_bytes, con
                d_token_type_ids, d_attention_mask, d_special_tokens_mask,
                {d_lab_bytes, d_lab_off, d_pos, d_pos_off}, d_labels, d_loss_mask, ignore_index, 0,
                {}};
-  return launch_rows(encode_kernel<false>, E, batch, 2, seq_len, stream);  // ids and labels
+  return launch_rows(encode_kernel<EncodeArgs>, E, batch, 2, seq_len, stream);  // ids and labels
 }
 
 // lddl_collate_encode_masked, lddl_collate_encode_masked_ww and (span given)
@@ -339,10 +311,14 @@ static int collate_encode_masked(lddl_ctx* c, void* stream, const uint8_t* d_byt
                                         counter)},
                           cont_bits_of(c)},
                          span ? *span : SpanDraw{}};
-  if (span) return launch_rows(encode_kernel<true, true>, E, batch, 2, seq_len, stream);
-  return whole_word
-             ? launch_rows(encode_kernel<true>, (const EncodeWwArgs&)E, batch, 2, seq_len, stream)
-             : launch_rows(encode_kernel<false>, (const EncodeArgs&)E, batch, 2, seq_len, stream);
+  const EncodeWwArgs& W = E;  // each kernel takes the part of E it was written for
+  const EncodeArgs& P = E;
+  switch (fused_mode(whole_word, span)) {
+    case kFusedSpan:
+      return launch_rows(encode_kernel<EncodeSpanArgs>, E, batch, 2, seq_len, stream);
+    case kFusedWw: return launch_rows(encode_kernel<EncodeWwArgs>, W, batch, 2, seq_len, stream);
+    default: return launch_rows(encode_kernel<EncodeArgs>, P, batch, 2, seq_len, stream);  // kFused
+  }
 }
 
 extern "C" int lddl_collate_encode(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
@@ -378,6 +354,34 @@ extern "C" int lddl_collate_encode_mp(lddl_ctx* c, void* stream, const uint8_t* 
                         ignore_index);
 }
 
+// What the three lddl_mask_dynamic* entry points refuse, in their order, and the arguments of
+// their kernels (native mode: lddl_mask_dynamic adds its replay pointers). An empty batch is
+// refused like a full one; each entry point returns 0 for it afterwards, by its own rule.
+static int mask_args_of(lddl_ctx* c, int64_t* d_input_ids, int64_t* d_labels,
+                        const int64_t* d_special_tokens_mask, const int32_t* d_na,
+                        const int32_t* d_nb, int64_t batch, int64_t seq_len, float mlm_probability,
+                        int64_t ignore_index, int64_t vocab_len, uint64_t seed, uint64_t counter,
+                        MaskArgs* M) {
+  if (!c) LDDL_FAIL(-1, "null ctx");
+  if (!d_special_tokens_mask && (!d_na != !d_nb)) LDDL_FAIL(-1, "need both lengths or neither");
+  if (c->tab.special_id[kMask] < 0) LDDL_FAIL(-1, "vocab has no [MASK]");
+  *M = MaskArgs{d_input_ids, d_labels, d_special_tokens_mask, d_na, d_nb, batch, seq_len,
+                mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, {}, seed,
+                counter, nullptr, nullptr, nullptr, nullptr};
+  for (int k = 0; k < kNumSpecial; ++k) M->special_ids[k] = c->tab.special_id[k];
+  return 0;
+}
+
+// mask_words_kernel over M's rows, kWwWaves of them per block; S: the span arguments, or nothing
+template <int MODE, typename... Span>
+static int launch_mask_words(lddl_ctx* c, void* stream, const MaskArgs& M, const Span&... S) {
+  hipLaunchKernelGGL((mask_words_kernel<MODE, Span...>),
+                     dim3((unsigned)((M.B + kWwWaves - 1) / kWwWaves)), dim3(64 * kWwWaves), 0,
+                     as_stream(stream), M, cont_bits_of(c), S...);
+  LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" int lddl_mask_dynamic(lddl_ctx* c, void* stream, int64_t* d_input_ids, int64_t* d_labels,
                                  const int64_t* d_special_tokens_mask, const int32_t* d_na,
                                  const int32_t* d_nb, int64_t batch, int64_t seq_len,
@@ -385,15 +389,14 @@ extern "C" int lddl_mask_dynamic(lddl_ctx* c, void* stream, int64_t* d_input_ids
                                  uint64_t seed, uint64_t counter, const uint8_t* d_r_masked,
                                  const uint8_t* d_r_replaced, const uint8_t* d_r_random,
                                  const int64_t* d_r_words) {
-  if (!c) LDDL_FAIL(-1, "null ctx");
-  if (!d_special_tokens_mask && (!d_na != !d_nb)) LDDL_FAIL(-1, "need both lengths or neither");
-  if (c->tab.special_id[kMask] < 0) LDDL_FAIL(-1, "vocab has no [MASK]");
+  MaskArgs M;
+  if (mask_args_of(c, d_input_ids, d_labels, d_special_tokens_mask, d_na, d_nb, batch, seq_len,
+                   mlm_probability, ignore_index, vocab_len, seed, counter, &M))
+    return -1;
   const int64_t n = batch * seq_len;
   if (n <= 0) return 0;
-  MaskArgs M{d_input_ids, d_labels, d_special_tokens_mask, d_na, d_nb, batch, seq_len,
-             mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, {}, seed, counter,
-             d_r_masked, d_r_replaced, d_r_random, d_r_words};
-  for (int k = 0; k < kNumSpecial; ++k) M.special_ids[k] = c->tab.special_id[k];
+  M.r_masked = d_r_masked, M.r_replaced = d_r_replaced, M.r_random = d_r_random;
+  M.r_words = d_r_words;
   hipLaunchKernelGGL(mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      as_stream(stream), M);
   LDDL_HIP(hipGetLastError());
@@ -418,19 +421,12 @@ extern "C" int lddl_mask_dynamic_ww(lddl_ctx* c, void* stream, int64_t* d_input_
                                     const int32_t* d_na, const int32_t* d_nb, int64_t batch,
                                     int64_t seq_len, float mlm_probability, int64_t ignore_index,
                                     int64_t vocab_len, uint64_t seed, uint64_t counter) {
-  if (!c) LDDL_FAIL(-1, "null ctx");
-  if (!d_special_tokens_mask && (!d_na != !d_nb)) LDDL_FAIL(-1, "need both lengths or neither");
-  if (c->tab.special_id[kMask] < 0) LDDL_FAIL(-1, "vocab has no [MASK]");
+  MaskArgs M;
+  if (mask_args_of(c, d_input_ids, d_labels, d_special_tokens_mask, d_na, d_nb, batch, seq_len,
+                   mlm_probability, ignore_index, vocab_len, seed, counter, &M))
+    return -1;
   if (batch <= 0 || seq_len <= 0) return 0;
-  MaskArgs M{d_input_ids, d_labels, d_special_tokens_mask, d_na, d_nb, batch, seq_len,
-             mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, {}, seed, counter,
-             nullptr, nullptr, nullptr, nullptr};
-  for (int k = 0; k < kNumSpecial; ++k) M.special_ids[k] = c->tab.special_id[k];
-  hipLaunchKernelGGL(mask_ww_kernel, dim3((unsigned)((batch + kWwWaves - 1) / kWwWaves)),
-                     dim3(64 * kWwWaves), 0, as_stream(stream), M,
-                     cont_bits_of(c));
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  return launch_mask_words<kFusedWw>(c, stream, M);
 }
 
 extern "C" int lddl_collate_encode_masked_ww(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
@@ -455,17 +451,12 @@ extern "C" int lddl_mask_dynamic_span(lddl_ctx* c, void* stream, int64_t* d_inpu
   if (!c) LDDL_FAIL(-1, "null ctx");
   SpanDraw S;
   if (span_draw_of(params, seed, &S)) return -1;
-  if (!d_special_tokens_mask && (!d_na != !d_nb)) LDDL_FAIL(-1, "need both lengths or neither");
-  if (c->tab.special_id[kMask] < 0) LDDL_FAIL(-1, "vocab has no [MASK]");
+  MaskArgs M;
+  if (mask_args_of(c, d_input_ids, d_labels, d_special_tokens_mask, d_na, d_nb, batch, seq_len,
+                   mlm_probability, ignore_index, vocab_len, seed, counter, &M))
+    return -1;
   if (batch <= 0 || seq_len <= 0) return 0;
-  MaskArgs M{d_input_ids, d_labels, d_special_tokens_mask, d_na, d_nb, batch, seq_len,
-             mlm_probability, ignore_index, c->tab.special_id[kMask], vocab_len, {}, seed, counter,
-             nullptr, nullptr, nullptr, nullptr};
-  for (int k = 0; k < kNumSpecial; ++k) M.special_ids[k] = c->tab.special_id[k];
-  hipLaunchKernelGGL(mask_span_kernel, dim3((unsigned)((batch + kWwWaves - 1) / kWwWaves)),
-                     dim3(64 * kWwWaves), 0, as_stream(stream), M, cont_bits_of(c), S);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  return launch_mask_words<kFusedSpan>(c, stream, M, S);
 }
 
 extern "C" int lddl_collate_encode_masked_span(

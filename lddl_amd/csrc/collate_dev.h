@@ -1,6 +1,7 @@
 // Device helpers shared by the collate kernels (collate.hip, collate_seqpack.hip,
 // collate_pairs.hip, collate_pairs_seqpack.hip): the exact vocab lookup of a whitespace-split
-// string, the per-slot Philox masking decision and the whole-word ballot, the MODE enum, the
+// string, the per-slot Philox masking decision and the whole-word ballot (the n-gram decision
+// is span_dev.h's), the MODE enum, the
 // slot layout of a sample (SlotLayout), the arguments of a string sample (StrSample, StrLabels)
 // and the read side of a pair table (PairTable, load_id, PairSlots, scatter_labels). The
 // kernels keep their loops and stores. The host side of the same units is collate_host.h.
@@ -138,8 +139,8 @@ enum { kPlain = 0, kFused = 1, kFusedWw = 2, kFusedSpan = 3 };
 // na + nb + 3 slots in all. X is the caller's slot type (int32_t, or int64_t in mask_kernel).
 // The layout refers to the caller's na and end, as a [&] lambda would, and does not copy them:
 // with copies the compiler promotes the values in another order and the kernels' code changes
-// (DESIGN §21). The string kernels and the whole-word loops write the predicates out for the
-// same reason.
+// (DESIGN §21). The string kernels and the word loops (one per kernel for whole-word and span,
+// DESIGN §26) write the predicates out for the same reason.
 struct SlotLayout {
   const int32_t& na;
   const int32_t& end;

@@ -53,6 +53,11 @@ inline int span_draw_of(const lddl_span_params* sp, uint64_t seed, SpanDraw* out
   return 0;
 }
 
+// the MODE of a fused-masking entry point: the span arguments given, else the whole-word flag
+inline int fused_mode(bool whole_word, const SpanDraw* span) {
+  return span ? kFusedSpan : whole_word ? kFusedWw : kFused;
+}
+
 // One wave per sample, kEncWaves samples per block, `words` int32 of LDS per slot and wave.
 template <typename Args>
 int launch_rows(void (*kernel)(Args), const Args& args, int32_t B, int words, int32_t L,

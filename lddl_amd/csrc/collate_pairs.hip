@@ -13,7 +13,8 @@
 // scatter (scatter_labels); the masking decision of a slot is collate_dev.h's too (MaskDraw,
 // mask_draw, mask_apply, word_masked, ContBits), with the same Philox index i * seq_len + x: the
 // mask stream is the string kernels' by construction. This unit owns the three row loops and
-// their stores; the whole-word loop writes its two predicates out (collate_dev.h says why).
+// their stores; the word loop, one for whole-word and span, writes its two
+// predicates out (collate_dev.h says why).
 //
 //   lddl_collate_pairs          lddl_collate_encode: unmasked (special_tokens_mask) or static
 //                               (labels scattered from pos / labels through one LDS row per wave,
@@ -65,10 +66,11 @@ __global__ void __launch_bounds__(64 * kEncWaves) pairs_kernel(PairsArgs E) {
 
   const PairSlots<ID> slot_id{E.P, t0, lay, E.cls, E.sep};  // the id before masking (x < L)
 
-  if constexpr (MODE == kFusedSpan) {
-    // the whole-word windows below with span_masked for word_masked: every lane reaches its
-    // ballot and its scan
-    int32_t words_before = 0;
+  if constexpr (MODE == kFusedWw || MODE == kFusedSpan) {
+    // windows of 64 slots up to a multiple of 64, the tail predicated: every lane reaches the
+    // ballots (and with kFusedSpan the scan) of the word-unit step
+    bool carry = false;        // kFusedWw: the state of word_masked between the row's windows
+    int32_t words_before = 0;  // kFusedSpan: that of span_masked
     uint32_t carry_max = 0;
     for (int32_t x0 = 0; x0 < E.L; x0 += 64) {
       const int32_t x = x0 + lane;
@@ -78,30 +80,12 @@ __global__ void __launch_bounds__(64 * kEncWaves) pairs_kernel(PairsArgs E) {
       const int32_t id = in ? slot_id(x) : 0;
       const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
       const uint4 r = mask_draw(E.draw, row + x);
-      const bool m = span_masked(E.span, E.draw.counter, in && !special && !cont, r, row + x,
-                                 words_before, carry_max);
-      if (in) {
-        int64_t lab;
-        E.input_ids[row + x] = mask_apply(E.draw, r, !special && m, id, &lab);
-        E.labels[row + x] = lab;
-        E.token_type_ids[row + x] = lay.segment(x);
-        E.attention_mask[row + x] = lay.real(x) ? 1 : 0;
-      }
-    }
-    return;
-  } else if constexpr (MODE == kFusedWw) {
-    // windows of 64 slots up to a multiple of 64, the tail predicated: every lane reaches the
-    // ballots of word_masked
-    bool carry = false;
-    for (int32_t x0 = 0; x0 < E.L; x0 += 64) {
-      const int32_t x = x0 + lane;
-      const bool in = x < E.L;
-      const bool special = x == 0 || x == na + 1 || x >= end - 1;
-      const bool prev_special = x <= 1 || x - 1 == na + 1 || x - 1 >= end - 1;  // of slot x - 1
-      const int32_t id = in ? slot_id(x) : 0;
-      const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
-      const uint4 r = mask_draw(E.draw, row + x);
-      const bool m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
+      bool m;  // the one line in which the two word modes differ
+      if constexpr (MODE == kFusedSpan)
+        m = span_masked(E.span, E.draw.counter, in && !special && !cont, r, row + x,
+                        words_before, carry_max);
+      else
+        m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
       if (in) {
         int64_t lab;
         E.input_ids[row + x] = mask_apply(E.draw, r, !special && m, id, &lab);
@@ -173,16 +157,15 @@ extern "C" int lddl_collate_pairs(lddl_ctx* c, void* stream, const void* d_token
   return launch<kPlain>(c, E, stream);
 }
 
-extern "C" int lddl_collate_pairs_masked(lddl_ctx* c, void* stream, const void* d_tokens,
-                                         const int64_t* d_tok_off, const int32_t* d_len_a,
-                                         const uint8_t* d_is_rn, const int64_t* d_rows,
-                                         int32_t batch, int32_t seq_len, int64_t* d_input_ids,
-                                         int64_t* d_token_type_ids, int64_t* d_attention_mask,
-                                         int64_t* d_labels, int64_t* d_next_sentence_labels,
-                                         float mlm_probability, int64_t ignore_index,
-                                         int64_t vocab_len, uint64_t seed, uint64_t counter,
-                                         int32_t whole_word) {
-  if (!c) LDDL_FAIL(-1, "null ctx");
+// lddl_collate_pairs_masked and, with the span arguments (already validated),
+// lddl_collate_pairs_masked_span
+static int pairs_masked(lddl_ctx* c, void* stream, const void* d_tokens, const int64_t* d_tok_off,
+                        const int32_t* d_len_a, const uint8_t* d_is_rn, const int64_t* d_rows,
+                        int32_t batch, int32_t seq_len, int64_t* d_input_ids,
+                        int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_labels,
+                        int64_t* d_next_sentence_labels, float mlm_probability,
+                        int64_t ignore_index, int64_t vocab_len, uint64_t seed, uint64_t counter,
+                        bool whole_word, const SpanDraw* span) {
   if (batch <= 0 || seq_len <= 0) return 0;
   if (need_vocab(c, true)) return -1;
   if (!d_tokens || !d_tok_off || !d_len_a || !d_is_rn) LDDL_FAIL(-1, "null pair table");
@@ -194,8 +177,28 @@ extern "C" int lddl_collate_pairs_masked(lddl_ctx* c, void* stream, const void* 
               d_token_type_ids, d_attention_mask, nullptr, d_labels, d_next_sentence_labels,
               ignore_index,
               mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
-              cont_bits_of(c), {}};
-  return whole_word ? launch<kFusedWw>(c, E, stream) : launch<kFused>(c, E, stream);
+              cont_bits_of(c), span ? *span : SpanDraw{}};
+  switch (fused_mode(whole_word, span)) {
+    case kFusedSpan: return launch<kFusedSpan>(c, E, stream);
+    case kFusedWw: return launch<kFusedWw>(c, E, stream);
+    default: return launch<kFused>(c, E, stream);
+  }
+}
+
+extern "C" int lddl_collate_pairs_masked(lddl_ctx* c, void* stream, const void* d_tokens,
+                                         const int64_t* d_tok_off, const int32_t* d_len_a,
+                                         const uint8_t* d_is_rn, const int64_t* d_rows,
+                                         int32_t batch, int32_t seq_len, int64_t* d_input_ids,
+                                         int64_t* d_token_type_ids, int64_t* d_attention_mask,
+                                         int64_t* d_labels, int64_t* d_next_sentence_labels,
+                                         float mlm_probability, int64_t ignore_index,
+                                         int64_t vocab_len, uint64_t seed, uint64_t counter,
+                                         int32_t whole_word) {
+  if (!c) LDDL_FAIL(-1, "null ctx");
+  return pairs_masked(c, stream, d_tokens, d_tok_off, d_len_a, d_is_rn, d_rows, batch, seq_len,
+                      d_input_ids, d_token_type_ids, d_attention_mask, d_labels,
+                      d_next_sentence_labels, mlm_probability, ignore_index, vocab_len, seed,
+                      counter, whole_word != 0, nullptr);
 }
 
 extern "C" int lddl_collate_pairs_masked_span(
@@ -208,17 +211,8 @@ extern "C" int lddl_collate_pairs_masked_span(
   if (!c) LDDL_FAIL(-1, "null ctx");
   SpanDraw S;
   if (span_draw_of(params, seed, &S)) return -1;
-  if (batch <= 0 || seq_len <= 0) return 0;
-  if (need_vocab(c, true)) return -1;
-  if (!d_tokens || !d_tok_off || !d_len_a || !d_is_rn) LDDL_FAIL(-1, "null pair table");
-  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels ||
-      !d_next_sentence_labels)
-    LDDL_FAIL(-1, "null output");
-  PairsArgs E{{d_tokens, d_tok_off, d_len_a, d_is_rn, nullptr, nullptr, nullptr, d_rows}, batch,
-              seq_len, c->tab.special_id[kCls], c->tab.special_id[kSep], d_input_ids,
-              d_token_type_ids, d_attention_mask, nullptr, d_labels, d_next_sentence_labels,
-              ignore_index,
-              mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
-              cont_bits_of(c), S};
-  return launch<kFusedSpan>(c, E, stream);
+  return pairs_masked(c, stream, d_tokens, d_tok_off, d_len_a, d_is_rn, d_rows, batch, seq_len,
+                      d_input_ids, d_token_type_ids, d_attention_mask, d_labels,
+                      d_next_sentence_labels, mlm_probability, ignore_index, vocab_len, seed,
+                      counter, true, &S);
 }

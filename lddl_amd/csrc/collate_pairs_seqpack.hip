@@ -10,7 +10,8 @@
 // plus position_ids = x and sequence_ids = seq_in_row[i]; slots [len, fill) are the row's tail:
 // 0 everywhere, labels ignore_index, special_tokens_mask 1. The slot's id, the layout and the
 // label scatter are collate_dev.h's (PairSlots, SlotLayout, scatter_labels), shared with
-// pairs_kernel; this unit owns the plan's prologue, the predicated window loop and its stores.
+// pairs_kernel; this unit owns the plan's prologue, the predicated window loop and its stores,
+// the loop's word branch once for whole-word and span.
 // The segments tile the outputs, so
 // every element is written once and nothing is cleared beforehand. The per-sample outputs
 // (next_sentence_labels, cls_positions, seq_lens) are written by the sample's wave at
@@ -96,10 +97,10 @@ __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
   // sample (refused on the host, dropped here)
   if (MODE == kPlain && E.P.pos) scatter_labels<ID>(E.P, q, slab, end, lane);
 
-  // 64-slot windows from the sample's start, the tail predicated: with MODE == kFusedWw every
-  // lane reaches the ballots of word_masked, with kFusedSpan the ballot and scan of span_masked
-  bool carry = false;
-  int32_t words_before = 0;  // kFusedSpan: the state of span_masked, per sample like carry
+  // 64-slot windows from the sample's start, the tail predicated: in the two word modes every
+  // lane reaches the ballots (and with kFusedSpan the scan) of the word-unit step
+  bool carry = false;        // kFusedWw: the state of word_masked, per sample
+  int32_t words_before = 0;  // kFusedSpan: that of span_masked, per sample like carry
   uint32_t carry_max = 0;
   for (int32_t x0 = 0; x0 < fill; x0 += 64) {
     const int32_t x = x0 + lane;
@@ -107,18 +108,16 @@ __global__ void __launch_bounds__(64 * kEncWaves) pack_kernel(PackArgs E) {
     const bool special = lay.special(x);
     const int32_t id = in ? slot_id(x) : 0;
     int64_t out = id, lab = E.ignore_index;
-    if constexpr (MODE == kFusedWw) {
+    if constexpr (MODE == kFusedWw || MODE == kFusedSpan) {
       const bool prev_special = x <= 1 || x - 1 == na + 1 || x - 1 >= end - 1;  // of slot x - 1
       const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
       const uint4 r = mask_draw(E.draw, flat + x);
-      const bool m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
-      out = mask_apply(E.draw, r, !special && m, id, &lab);
-    } else if constexpr (MODE == kFusedSpan) {
-      const bool prev_special = x <= 1 || x - 1 == na + 1 || x - 1 >= end - 1;  // of slot x - 1
-      const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
-      const uint4 r = mask_draw(E.draw, flat + x);
-      const bool m = span_masked(E.span, E.draw.counter, in && !special && !cont, r, flat + x,
-                                 words_before, carry_max);
+      bool m;  // the one line in which the two word modes differ
+      if constexpr (MODE == kFusedSpan)
+        m = span_masked(E.span, E.draw.counter, in && !special && !cont, r, flat + x,
+                        words_before, carry_max);
+      else
+        m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
       out = mask_apply(E.draw, r, !special && m, id, &lab);
     } else if constexpr (MODE == kFused) {
       if (real) out = mask_slot(E.draw, flat + x, special, id, &lab);
@@ -182,16 +181,21 @@ extern "C" int lddl_collate_pairs_seqpack(
   return launch<kPlain>(c, E, stream);
 }
 
-extern "C" int lddl_collate_pairs_seqpack_masked(
-    lddl_ctx* c, void* stream, const void* d_tokens, const int64_t* d_tok_off,
-    const int32_t* d_len_a, const uint8_t* d_is_rn, const int64_t* d_rows, int32_t batch,
-    const int64_t* d_dst, const int32_t* d_fill, const int32_t* d_seq_in_row,
-    const int32_t* d_packed_idx, int32_t out_rows, int32_t max_seq_length, int32_t draw_stride,
-    int64_t* d_input_ids, int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_labels,
-    int64_t* d_position_ids, int64_t* d_sequence_ids, int64_t* d_next_sentence_labels,
-    int64_t* d_cls_positions, int32_t* d_seq_lens, float mlm_probability, int64_t ignore_index,
-    int64_t vocab_len, uint64_t seed, uint64_t counter, int32_t whole_word) {
-  if (!c) LDDL_FAIL(-1, "null ctx");
+// lddl_collate_pairs_seqpack_masked and, with the span arguments (already validated),
+// lddl_collate_pairs_seqpack_masked_span
+static int pairs_seqpack_masked(lddl_ctx* c, void* stream, const void* d_tokens,
+                                const int64_t* d_tok_off, const int32_t* d_len_a,
+                                const uint8_t* d_is_rn, const int64_t* d_rows, int32_t batch,
+                                const int64_t* d_dst, const int32_t* d_fill,
+                                const int32_t* d_seq_in_row, const int32_t* d_packed_idx,
+                                int32_t out_rows, int32_t max_seq_length, int32_t draw_stride,
+                                int64_t* d_input_ids, int64_t* d_token_type_ids,
+                                int64_t* d_attention_mask, int64_t* d_labels,
+                                int64_t* d_position_ids, int64_t* d_sequence_ids,
+                                int64_t* d_next_sentence_labels, int64_t* d_cls_positions,
+                                int32_t* d_seq_lens, float mlm_probability, int64_t ignore_index,
+                                int64_t vocab_len, uint64_t seed, uint64_t counter,
+                                bool whole_word, const SpanDraw* span) {
   if (batch <= 0 || out_rows <= 0 || max_seq_length <= 0) return 0;
   if (need_vocab(c, true)) return -1;
   if (!d_tokens || !d_tok_off || !d_len_a || !d_is_rn) LDDL_FAIL(-1, "null pair table");
@@ -205,8 +209,30 @@ extern "C" int lddl_collate_pairs_seqpack_masked(
              d_attention_mask, nullptr, d_labels, d_position_ids, d_sequence_ids,
              d_next_sentence_labels, d_cls_positions, d_seq_lens, ignore_index,
              mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
-             cont_bits_of(c), {}};
-  return whole_word ? launch<kFusedWw>(c, E, stream) : launch<kFused>(c, E, stream);
+             cont_bits_of(c), span ? *span : SpanDraw{}};
+  switch (fused_mode(whole_word, span)) {
+    case kFusedSpan: return launch<kFusedSpan>(c, E, stream);
+    case kFusedWw: return launch<kFusedWw>(c, E, stream);
+    default: return launch<kFused>(c, E, stream);
+  }
+}
+
+extern "C" int lddl_collate_pairs_seqpack_masked(
+    lddl_ctx* c, void* stream, const void* d_tokens, const int64_t* d_tok_off,
+    const int32_t* d_len_a, const uint8_t* d_is_rn, const int64_t* d_rows, int32_t batch,
+    const int64_t* d_dst, const int32_t* d_fill, const int32_t* d_seq_in_row,
+    const int32_t* d_packed_idx, int32_t out_rows, int32_t max_seq_length, int32_t draw_stride,
+    int64_t* d_input_ids, int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_labels,
+    int64_t* d_position_ids, int64_t* d_sequence_ids, int64_t* d_next_sentence_labels,
+    int64_t* d_cls_positions, int32_t* d_seq_lens, float mlm_probability, int64_t ignore_index,
+    int64_t vocab_len, uint64_t seed, uint64_t counter, int32_t whole_word) {
+  if (!c) LDDL_FAIL(-1, "null ctx");
+  return pairs_seqpack_masked(c, stream, d_tokens, d_tok_off, d_len_a, d_is_rn, d_rows, batch,
+                              d_dst, d_fill, d_seq_in_row, d_packed_idx, out_rows, max_seq_length,
+                              draw_stride, d_input_ids, d_token_type_ids, d_attention_mask,
+                              d_labels, d_position_ids, d_sequence_ids, d_next_sentence_labels,
+                              d_cls_positions, d_seq_lens, mlm_probability, ignore_index, vocab_len,
+                              seed, counter, whole_word != 0, nullptr);
 }
 
 extern "C" int lddl_collate_pairs_seqpack_masked_span(
@@ -221,19 +247,10 @@ extern "C" int lddl_collate_pairs_seqpack_masked_span(
   if (!c) LDDL_FAIL(-1, "null ctx");
   SpanDraw S;
   if (span_draw_of(params, seed, &S)) return -1;
-  if (batch <= 0 || out_rows <= 0 || max_seq_length <= 0) return 0;
-  if (need_vocab(c, true)) return -1;
-  if (!d_tokens || !d_tok_off || !d_len_a || !d_is_rn) LDDL_FAIL(-1, "null pair table");
-  if (!d_dst || !d_fill || !d_seq_in_row || !d_packed_idx) LDDL_FAIL(-1, "null plan");
-  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels || !d_position_ids ||
-      !d_sequence_ids || !d_next_sentence_labels || !d_cls_positions || !d_seq_lens)
-    LDDL_FAIL(-1, "null output");
-  PackArgs E{{d_tokens, d_tok_off, d_len_a, d_is_rn, nullptr, nullptr, nullptr, d_rows}, d_dst,
-             d_fill, d_seq_in_row, d_packed_idx, batch, out_rows, max_seq_length, draw_stride,
-             c->tab.special_id[kCls], c->tab.special_id[kSep], d_input_ids, d_token_type_ids,
-             d_attention_mask, nullptr, d_labels, d_position_ids, d_sequence_ids,
-             d_next_sentence_labels, d_cls_positions, d_seq_lens, ignore_index,
-             mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
-             cont_bits_of(c), S};
-  return launch<kFusedSpan>(c, E, stream);
+  return pairs_seqpack_masked(c, stream, d_tokens, d_tok_off, d_len_a, d_is_rn, d_rows, batch,
+                              d_dst, d_fill, d_seq_in_row, d_packed_idx, out_rows, max_seq_length,
+                              draw_stride, d_input_ids, d_token_type_ids, d_attention_mask,
+                              d_labels, d_position_ids, d_sequence_ids, d_next_sentence_labels,
+                              d_cls_positions, d_seq_lens, mlm_probability, ignore_index, vocab_len,
+                              seed, counter, true, &S);
 }

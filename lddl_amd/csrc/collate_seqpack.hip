@@ -12,7 +12,8 @@
 // written exactly once and nothing is cleared beforehand. One wave per sample, the segment
 // staged in LDS as in encode_kernel, whose string-side arguments it shares (collate_dev.h's
 // StrSample, StrLabels); the staging and the window loop are written out here, as the comment
-// at collate_dev.h's SlotLayout explains. The Philox index of slot x of sample i is
+// at collate_dev.h's SlotLayout explains, the loop's word branch once for whole-word and span
+// (DESIGN §26). The Philox index of slot x of sample i is
 // i * draw_stride + x: the masking is that of the unpacked batch, whatever the layout.
 #include "collate_host.h"  // need_vocab, launch_rows; collate_dev.h
 #include "lddl_amd.h"
@@ -77,29 +78,27 @@ __global__ void __launch_bounds__(64 * kEncWaves) seqpack_kernel(SeqpackArgs E) 
   const int64_t o = E.dst[b];
   const int64_t flat = (int64_t)b * E.draw_stride;
   const int64_t seq = E.seq_in_row[b];
-  bool carry = false;
-  int32_t words_before = 0;  // kFusedSpan: the state of span_masked, per sample like carry
+  bool carry = false;        // kFusedWw: the state of word_masked, per sample
+  int32_t words_before = 0;  // kFusedSpan: that of span_masked, per sample like carry
   uint32_t carry_max = 0;
-  // 64-slot windows from the sample's start, the tail predicated: with MODE == kFusedWw every
-  // lane reaches the ballots of word_masked, with kFusedSpan the ballot and scan of span_masked
+  // 64-slot windows from the sample's start, the tail predicated: in the two word modes every
+  // lane reaches the ballots (and with kFusedSpan the scan) of the word-unit step
   for (int32_t x0 = 0; x0 < fill; x0 += 64) {
     const int32_t x = x0 + lane;
     const bool in = x < fill, real = x < end;
     const bool special = x == 0 || x == na + 1 || x >= end - 1;
     const int32_t id = in ? sid[x] : 0;
     int64_t out = id, lab = E.ignore_index;
-    if constexpr (MODE == kFusedWw) {
+    if constexpr (MODE == kFusedWw || MODE == kFusedSpan) {
       const bool prev_special = x <= 1 || x - 1 == na + 1 || x - 1 >= end - 1;  // of slot x - 1
       const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
       const uint4 r = mask_draw(E.draw, flat + x);
-      const bool m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
-      out = mask_apply(E.draw, r, !special && m, id, &lab);
-    } else if constexpr (MODE == kFusedSpan) {
-      const bool prev_special = x <= 1 || x - 1 == na + 1 || x - 1 >= end - 1;  // of slot x - 1
-      const bool cont = in && !special && !prev_special && cont_id(E.cont, id);
-      const uint4 r = mask_draw(E.draw, flat + x);
-      const bool m = span_masked(E.span, E.draw.counter, in && !special && !cont, r, flat + x,
-                                 words_before, carry_max);
+      bool m;  // the one line in which the two word modes differ
+      if constexpr (MODE == kFusedSpan)
+        m = span_masked(E.span, E.draw.counter, in && !special && !cont, r, flat + x,
+                        words_before, carry_max);
+      else
+        m = word_masked(!cont, u01(r.x) < E.draw.p, lane, carry);
       out = mask_apply(E.draw, r, !special && m, id, &lab);
     } else if constexpr (MODE == kFused) {
       if (real) out = mask_slot(E.draw, flat + x, special, id, &lab);
@@ -157,6 +156,34 @@ extern "C" int lddl_collate_seqpack(lddl_ctx* c, void* stream, const uint8_t* d_
   return launch<kPlain>(E, stream);
 }
 
+// lddl_collate_seqpack_masked and, with the span arguments (already validated),
+// lddl_collate_seqpack_masked_span
+static int seqpack_masked(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
+                          const int64_t* d_a_off, const int64_t* d_b_off, const int32_t* d_na,
+                          const int32_t* d_nb, int32_t batch, const int64_t* d_dst,
+                          const int32_t* d_fill, const int32_t* d_seq_in_row,
+                          int32_t max_seq_length, int32_t draw_stride, int64_t* d_input_ids,
+                          int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_labels,
+                          int64_t* d_position_ids, int64_t* d_sequence_ids, float mlm_probability,
+                          int64_t ignore_index, int64_t vocab_len, uint64_t seed, uint64_t counter,
+                          bool whole_word, const SpanDraw* span) {
+  if (batch <= 0 || max_seq_length <= 0) return 0;
+  if (need_vocab(c, true)) return -1;
+  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels || !d_position_ids ||
+      !d_sequence_ids || !d_dst || !d_fill || !d_seq_in_row)
+    LDDL_FAIL(-1, "null output");
+  SeqpackArgs E{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb}, d_dst, d_fill, d_seq_in_row,
+                batch, max_seq_length, d_input_ids, d_token_type_ids, d_attention_mask,
+                d_position_ids, d_sequence_ids, d_labels, nullptr, {}, ignore_index, draw_stride,
+                mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
+                cont_bits_of(c), span ? *span : SpanDraw{}};
+  switch (fused_mode(whole_word, span)) {
+    case kFusedSpan: return launch<kFusedSpan>(E, stream);
+    case kFusedWw: return launch<kFusedWw>(E, stream);
+    default: return launch<kFused>(E, stream);
+  }
+}
+
 extern "C" int lddl_collate_seqpack_masked(lddl_ctx* c, void* stream, const uint8_t* d_bytes,
                                            const int64_t* d_a_off, const int64_t* d_b_off,
                                            const int32_t* d_na, const int32_t* d_nb, int32_t batch,
@@ -169,17 +196,10 @@ extern "C" int lddl_collate_seqpack_masked(lddl_ctx* c, void* stream, const uint
                                            int64_t ignore_index, int64_t vocab_len, uint64_t seed,
                                            uint64_t counter, int32_t whole_word) {
   if (!c) LDDL_FAIL(-1, "null ctx");
-  if (batch <= 0 || max_seq_length <= 0) return 0;
-  if (need_vocab(c, true)) return -1;
-  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels || !d_position_ids ||
-      !d_sequence_ids || !d_dst || !d_fill || !d_seq_in_row)
-    LDDL_FAIL(-1, "null output");
-  SeqpackArgs E{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb}, d_dst, d_fill, d_seq_in_row,
-                batch, max_seq_length, d_input_ids, d_token_type_ids, d_attention_mask,
-                d_position_ids, d_sequence_ids, d_labels, nullptr, {}, ignore_index, draw_stride,
-                mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
-                cont_bits_of(c), {}};
-  return whole_word ? launch<kFusedWw>(E, stream) : launch<kFused>(E, stream);
+  return seqpack_masked(c, stream, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, d_dst, d_fill,
+                        d_seq_in_row, max_seq_length, draw_stride, d_input_ids, d_token_type_ids,
+                        d_attention_mask, d_labels, d_position_ids, d_sequence_ids, mlm_probability,
+                        ignore_index, vocab_len, seed, counter, whole_word != 0, nullptr);
 }
 
 extern "C" int lddl_collate_seqpack_masked_span(
@@ -193,15 +213,8 @@ extern "C" int lddl_collate_seqpack_masked_span(
   if (!c) LDDL_FAIL(-1, "null ctx");
   SpanDraw S;
   if (span_draw_of(params, seed, &S)) return -1;
-  if (batch <= 0 || max_seq_length <= 0) return 0;
-  if (need_vocab(c, true)) return -1;
-  if (!d_input_ids || !d_token_type_ids || !d_attention_mask || !d_labels || !d_position_ids ||
-      !d_sequence_ids || !d_dst || !d_fill || !d_seq_in_row)
-    LDDL_FAIL(-1, "null output");
-  SeqpackArgs E{{c->tab, d_bytes, d_a_off, d_b_off, d_na, d_nb}, d_dst, d_fill, d_seq_in_row,
-                batch, max_seq_length, d_input_ids, d_token_type_ids, d_attention_mask,
-                d_position_ids, d_sequence_ids, d_labels, nullptr, {}, ignore_index, draw_stride,
-                mask_draw_of(c, mlm_probability, ignore_index, vocab_len, seed, counter),
-                cont_bits_of(c), S};
-  return launch<kFusedSpan>(E, stream);
+  return seqpack_masked(c, stream, d_bytes, d_a_off, d_b_off, d_na, d_nb, batch, d_dst, d_fill,
+                        d_seq_in_row, max_seq_length, draw_stride, d_input_ids, d_token_type_ids,
+                        d_attention_mask, d_labels, d_position_ids, d_sequence_ids, mlm_probability,
+                        ignore_index, vocab_len, seed, counter, true, &S);
 }

@@ -1,6 +1,7 @@
 // N-gram (span) dynamic masking, the device side shared by the collate kernels: the
-// span arguments and one 64-slot window of the decision. The kernels keep their loops and stores
-// (collate_dev.h says why); each translation unit gets its own copy (anonymous namespace).
+// span arguments and one 64-slot window of the decision, which a kernel's one word loop calls in
+// place of word_masked. The kernels keep their loops and stores (collate_dev.h says
+// why); each translation unit gets its own copy (anonymous namespace).
 //
 // Words are counted over non-special slots; a non-special head h of word j starts a span iff its
 // own mask draw says so (u01(r(h).x) < p_start), the span's length in words comes from a second

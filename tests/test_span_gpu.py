@@ -269,7 +269,8 @@ def _seqpack_span(ctx, batch, L, align, mask, span):
     """lddl_collate_seqpack_masked_span called as the C ABI defines it, for `batch` planned into
     rows of L slots: the arguments of lddl_collate_seqpack_masked without the whole_word flag,
     plus the params. (encode_seqpacked, which stages the same arrays for the sibling, takes no
-    span argument.) Returns encode_seqpacked's dict."""
+    span argument.) span=None calls that sibling, lddl_collate_seqpack_masked with whole_word = 1,
+    on the same arrays. Returns encode_seqpacked's dict."""
     from lddl_amd._native import check, lib
     from lddl_amd.context import _ptr, _stream
     from lddl_amd.torch.bert import PackedBatch
@@ -291,12 +292,14 @@ def _seqpack_span(ctx, batch, L, align, mask, span):
            for k in ('input_ids', 'token_type_ids', 'attention_mask', 'labels', 'position_ids',
                      'sequence_ids')}
     p, seed, counter = mask
-    check(lib.lddl_collate_seqpack_masked_span(
+    entry, last = (lib.lddl_collate_seqpack_masked, 1) if span is None else \
+        (lib.lddl_collate_seqpack_masked_span, span.ptr(p))
+    check(entry(
         ctx.handle, _stream(), _ptr(d_blob), _ptr(d_a), _ptr(d_b), _ptr(d_na), _ptr(d_nb), B,
         _ptr(d_dst), _ptr(d_fill), _ptr(d_seq), L, stride, _ptr(out['input_ids']),
         _ptr(out['token_type_ids']), _ptr(out['attention_mask']), _ptr(out['labels']),
         _ptr(out['position_ids']), _ptr(out['sequence_ids']), float(p), IGN, len(ctx), seed,
-        counter, span.ptr(p)))
+        counter, last))
     order = plan.order
     out['next_sentence_labels'] = dev(np.asarray(pk.nsl)[order], np.int64)
     out['cls_positions'] = dev(dst[order], np.int64)
@@ -322,6 +325,82 @@ def test_packed_string_entry_point_equals_unpacked_rows(ctx_c, dyn_samples, pars
             assert_packed(got, unp, lens.tolist(), pk.nsl, L, IGN)
             n_masked += int((got['labels'] != IGN).sum())
     assert n_masked > 0
+
+
+# ---- the two word modes of each kernel's one loop against each other ----------------------------
+def _edge_pairs(words, cont):
+    """Five hand-made pairs of at most 128 slots: the last [SEP] on slot 63 and on slot 64 (the
+    whole-word carry and the span state both cross a window), a '##' piece at the head of B, a
+    pair that fills 128 slots and the smallest pair. A third of the ids are '##' pieces."""
+    rng = np.random.default_rng(26)
+
+    def ids(n):
+        return np.where(rng.random(n) < 0.33, cont[rng.integers(0, len(cont), n)],
+                        words[rng.integers(0, len(words), n)])
+    out = []
+    for slots, na in ((64, 30), (65, 31), (100, 40), (128, 70), (5, 1)):
+        t = ids(slots - 3)
+        out.append([t[:na], t[na:], bool(rng.integers(0, 2))])
+    out[2][1][0] = cont[7]  # B starts with a piece: behind [SEP] it is a head, not a continuation
+    out[0][0][-1], out[1][0][-1] = cont[3], cont[5]  # a word that ends against the middle [SEP]
+    return out
+
+
+def _same(a, b, what):
+    assert set(a) == set(b), what
+    for k in a:
+        assert torch.equal(a[k], b[k]), (what, k)
+    return int((a['labels'] != IGN).sum())
+
+
+@pytest.mark.parametrize('p', [0.15, 1.0])
+def test_n1_is_whole_word_masking_in_every_collate_kernel(ctx_u, ctx_c, dyn_samples, parsed, p):
+    """span=1 and whole_word=True run the same loop of each kernel with the other of its two
+    decisions: at equal (seed, counter) every output is bit-equal, through
+    encode_packed, collate_pairs (2-byte ids), collate_pairs_seqpacked and, through the C ABI,
+    lddl_collate_seqpack_masked / _masked_span. Batches of 5, packed rows of 128 slots."""
+    from lddl_amd.torch.bert import PackedBatch, encode_packed
+    from lddl_amd.torch.online import collate_pairs, collate_pairs_seqpacked, plan_rows_device
+    from test_online_seqpack_gpu import _pair_batch
+    n1, mask, L = parsed['n1'], (p, SEED, COUNTER), 128
+    assert ctx_u.id_bytes == 2
+    words, cont = _ascii_ids(ctx_u)
+    samples = _edge_pairs(words, cont)
+    lens = [len(a) + len(b) + 3 for a, b, _ in samples]
+    assert lens == [64, 65, 100, 128, 5] and len(samples) == 5
+    assert ctx_u.tokens[samples[2][1][0]].startswith('##')
+    pb = _pair_batch(ctx_u, samples)
+    assert pb.num_tokens.tolist() == lens
+    rendered = _tuples(ctx_u, pb)
+    # the fixture's samples that fit a packed row, the first five
+    short = [t for t in dyn_samples if len(t[0].split()) + len(t[1].split()) + 3 <= L][:5]
+    assert len(short) == 5
+    n_masked = 0
+    for ctx, batch in ((ctx_u, rendered), (ctx_c, short)):  # the string kernels
+        pk = PackedBatch(batch)
+        for align in (8, 64):
+            ww = encode_packed(pk, ctx, align, IGN, mask=mask, whole_word=True)
+            sp = encode_packed(pk, ctx, align, IGN, mask=mask, span=n1)
+            n_masked += _same(ww, sp, ('encode_packed', align))
+            ww = _seqpack_span(ctx, batch, L, align, mask, None)[0]
+            sp = _seqpack_span(ctx, batch, L, align, mask, n1)[0]
+            n_masked += _same(ww, sp, ('lddl_collate_seqpack_masked', align))
+    # the pair-table kernels
+    ww = collate_pairs(ctx_u, pb, None, 8, IGN, mask=mask, whole_word=True)
+    sp = collate_pairs(ctx_u, pb, None, 8, IGN, mask=mask, span=n1)
+    n_masked += _same(ww, sp, 'collate_pairs')
+    # (the hand-made pairs are the strings' ids: the table kernel sees what the string kernel saw)
+    assert torch.equal(ww['input_ids'],
+                       encode_packed(PackedBatch(rendered), ctx_u, 8, IGN, mask=mask,
+                                     whole_word=True)['input_ids'])
+    stride = ww['input_ids'].shape[1]
+    plan = plan_rows_device(ctx_u, pb, None, [0, 5], L)
+    ww = collate_pairs_seqpacked(ctx_u, pb, None, plan, 0, None, L, stride, IGN, mask=mask,
+                                 whole_word=True)
+    sp = collate_pairs_seqpacked(ctx_u, pb, None, plan, 0, None, L, stride, IGN, mask=mask,
+                                 span=n1)
+    n_masked += _same(ww, sp, 'collate_pairs_seqpacked')
+    assert n_masked > 100
 
 
 # ---- refusals -----------------------------------------------------------------------------------
