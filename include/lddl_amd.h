@@ -702,6 +702,38 @@ typedef struct {
 int lddl_span_params_make(double mlm_probability, int32_t n, const double* weights,
                           lddl_span_params* out);
 
+/* N-gram (span) static masking in the pair planner (past the reference):
+ * lddl_pairs_plan_head with one more argument. span = NULL is lddl_pairs_plan_head. Otherwise
+ * params->masking = 1 and params->rng = LDDL_RNG_NATIVE are needed and span must be one that
+ * lddl_span_params_make can have written (n and cum are read, p_start is not); any other case
+ * fails with -1 and a message naming span, before anything is allocated or launched.
+ * params->whole_word beside it changes nothing. Tail, emit, destroy and part offsets are the
+ * existing calls.
+ *   Words, specials, continuations and the budget (the per-token mode's num_to_predict) are
+ *   those of whole_word = 1; the words 0 .. W - 1 are numbered in token order. An n-gram is n
+ *   consecutive words j .. j + n - 1; it may run from A into B and over a literal [CLS]/[SEP],
+ *   which is never masked and does not count: tok(j, n) = the non-special tokens of those words.
+ *   Head h (a token index) of planner pair idx draws from its whole-word key block: the first
+ *   word is the order key, the second, y, the length
+ *     L(h) = 1 + #{k in [1, n) : u01(y) >= cum[k - 1]}.
+ *   The words are visited in the whole-word order (key, then token index mod 64, then token
+ *   index), each once, with masked = 0 and nothing covered at the start. For a visited word j:
+ *   stop if masked = budget; n = min(L(head_j), W - j) (clipped at the pair's end, not
+ *   renormalised); while n >= 1 and masked + tok(j, n) > budget, n -= 1; if n = 0, or any of the
+ *   words j .. j + n - 1 is covered (j itself included), go on to the next word (the start is
+ *   dropped, not shrunk); else cover them, mask their tokens and add tok(j, n) to masked.
+ *   80 / 10 / 10 and the random id come from the token's own decide block, as with whole_word.
+ * A pair may end below its budget, also at 0; counts[2] and pos_off are exact. n = 1 is
+ * bit-identical to whole_word = 1, and the pairs themselves are those of the per-token run.
+ * Not built: favor_longer_ngram, and length weights renormalised per start. */
+int lddl_pairs_plan_head_span(lddl_ctx* ctx, void* stream, const lddl_pair_params* params,
+                              const int64_t* d_sent_off, const int32_t* d_ids,
+                              const int32_t* d_sent_len, int64_t n_sent,
+                              const int64_t* d_doc_sent_off, int64_t n_doc,
+                              const int64_t* d_part_doc_off, const int64_t* d_part_seed,
+                              int64_t n_part, lddl_pairs** out, int64_t* head,
+                              const lddl_span_params* span);
+
 int lddl_mask_dynamic_span(lddl_ctx* ctx, void* stream, int64_t* d_input_ids, int64_t* d_labels,
                            const int64_t* d_special_tokens_mask, const int32_t* d_na,
                            const int32_t* d_nb, int64_t batch, int64_t seq_len,

@@ -125,6 +125,10 @@ SIGNATURES = {
     # n-gram (span) dynamic masking: the whole-word siblings' arguments (without the flag) and
     # a const lddl_span_params* (SpanParams below)
     'lddl_span_params_make': (ctypes.c_int, [c_dbl, c_i32, c_vp, c_vp]),
+    # n-gram static masking: lddl_pairs_plan_head's arguments and a const lddl_span_params*
+    'lddl_pairs_plan_head_span': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                                 c_i64, c_vp, c_vp, c_i64, ctypes.POINTER(c_vp),
+                                                 c_vp, c_vp]),
     'lddl_mask_dynamic_span': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
                                               c_i64, ctypes.c_float, c_i64, c_i64, c_u64, c_u64,
                                               c_vp]),

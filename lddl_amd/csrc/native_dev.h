@@ -132,8 +132,9 @@ __device__ inline CtrRng token_rng(uint64_t key, int64_t pair_index, uint32_t st
 
 }  // namespace
 
-// pairs_native_mask.hip: the masks of the plan's A.n_pairs pairs, by mask_native_kernel or (whole
-// word) mask_ww_native_kernel, on the planning stream; sets A.words
+// pairs_native_mask.hip: the masks of the plan's A.n_pairs pairs, by mask_native_kernel, (whole
+// word) mask_ww_native_kernel or (n-gram) mask_span_native_kernel, on the planning stream; sets
+// A.words
 void launch_native_masks(const lddl_pairs* P, const PlanWork& W, NativeArgs& A);
 
 }  // namespace lddl

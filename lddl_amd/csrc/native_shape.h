@@ -1,5 +1,6 @@
-// The launch shapes of the native planner's three dynamic-LDS kernels (plan_native_kernel,
-// pairs_native.hip; mask_native_kernel and mask_ww_native_kernel, pairs_native_mask.hip) as pure
+// The launch shapes of the native planner's four dynamic-LDS kernels (plan_native_kernel,
+// pairs_native.hip; mask_native_kernel, mask_ww_native_kernel and mask_span_native_kernel,
+// pairs_native_mask.hip) as pure
 // functions of the plan's parameters: the launch sites take every grid, block, LDS size and
 // shape argument from here and compute none. (Host-only and free of the HIP runtime, like
 // plan_split.h, so a CPU program can test it: tests/native_shape_check.cpp.)
@@ -73,6 +74,27 @@ inline WwShape native_ww_shape(int32_t seq) {
   s.seqp = (seq - 3 + 63) / 64 * 64;
   s.wave_bytes = (size_t)8 * (s.seqp + s.seqp / 64 + 1);
   s.waves = (int)std::max<size_t>(1, std::min<size_t>(4, kNativeMaskLds / s.wave_bytes));
+  return s;
+}
+
+// mask_span_native_kernel: one wave per pair; per wave an 8-byte entry per token of the longest
+// pair (as WwShape) and the word table, 4 bytes (head | tokens before << 16) per word and one
+// past the last, padded to keep the waves' entries 8-byte aligned; up to 4 waves within
+// kNativeMaskLds. The ballots stay in registers. seq 4096, the longest static masking takes,
+// asks for 48 KB: every seq fits.
+struct SpanShape {
+  int32_t seqp;       // tokens of the longest pair, in whole 64-token windows
+  size_t wave_bytes;  // LDS per wave
+  int waves;          // per workgroup (= pairs per workgroup), 1 .. 4; 0: seq does not fit
+  size_t lds_bytes() const { return wave_bytes * waves; }
+  unsigned threads() const { return 64u * (unsigned)waves; }
+  unsigned grid(int64_t n_pairs) const { return (unsigned)((n_pairs + waves - 1) / waves); }
+};
+inline SpanShape native_span_shape(int32_t seq) {
+  SpanShape s;
+  s.seqp = (seq - 3 + 63) / 64 * 64;
+  s.wave_bytes = (size_t)8 * s.seqp + (size_t)4 * (s.seqp + 2);
+  s.waves = (int)std::min<size_t>(4, kNativeMaskLds / s.wave_bytes);
   return s;
 }
 

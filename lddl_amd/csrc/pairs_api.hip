@@ -15,7 +15,7 @@
 //   densify_dev.h      one wave's share of the dense packing (the planner's dense workgroups too)
 //   pairs_densify.hip  the dense packing as launches of its own (launch_densify, launch_densify_head)
 //   pairs_native.hip   the native planner: the walk, the keyed order, plan_native
-//   pairs_native_mask.hip  its two mask kernels, plain and whole-word (launch_native_masks)
+//   pairs_native_mask.hip  its three mask kernels, plain, whole-word and n-gram (launch_native_masks)
 //   native_dev.h       what the two share on the device: the Philox streams, NativeArgs
 //   native_shape.h     the native launches' LDS sizes, grids and blocks (host-only)
 //   pairs_shuffle.hip  the replay plan's partition shuffle (shuffle_partitions)
@@ -49,12 +49,16 @@
 //           applying the mask decisions and emitting positions + labels.
 #include "pairs_plan.h"
 
+#include "collate_host.h"  // span_draw_of: the one check of a caller's lddl_span_params
+#include "native_shape.h"
+
 using namespace lddl;
 
 // static masking: the gather keeps a decision per token of the sequence in LDS (pairs_gather.hip)
 constexpr int kMaxSeqGather = 4096;
 
-static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, PlanKnobs* knobs) {
+static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, const lddl_span_params* span,
+                           PlanKnobs* knobs) {
   if (!c || !prm) LDDL_FAIL(-1, "null argument");
   if (prm->seq < 5 || prm->seq > 65535) LDDL_FAIL(-1, "target_seq_length %d out of range", prm->seq);
   if (prm->dup < 1) LDDL_FAIL(-1, "duplicate_factor must be >= 1");
@@ -69,6 +73,18 @@ static int check_plan_args(const lddl_ctx* c, const lddl_pair_params* prm, PlanK
   if (prm->whole_word && prm->rng != LDDL_RNG_NATIVE)
     LDDL_FAIL(-1, "whole_word needs rng = LDDL_RNG_NATIVE (the replay mode reproduces the "
                   "reference, which has no whole-word masking)");
+  if (span) {
+    if (!prm->masking) LDDL_FAIL(-1, "span (n-gram masking) needs static masking (masking = 1)");
+    if (prm->rng != LDDL_RNG_NATIVE)
+      LDDL_FAIL(-1, "span (n-gram masking) needs rng = LDDL_RNG_NATIVE (the replay mode reproduces "
+                    "the reference, which has no n-gram masking)");
+    SpanDraw draw;
+    int rc;
+    if ((rc = span_draw_of(span, 0, &draw))) return rc;
+    if (native_span_shape(prm->seq).waves < 1)
+      LDDL_FAIL(-1, "span (n-gram masking): target_seq_length %d does not fit the mask kernel's LDS",
+                prm->seq);
+  }
   return read_plan_knobs(knobs);
 }
 
@@ -177,17 +193,17 @@ static void plan_counts(const lddl_pairs* P, int64_t* counts) {
   counts[4] = P->n_kept_doc;
 }
 
-extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_params* prm,
-                                    const int64_t* d_sent_off, const int32_t* d_ids,
-                                    const int32_t* d_sent_len, int64_t n_sent,
-                                    const int64_t* d_doc_sent_off, int64_t n_doc,
-                                    const int64_t* d_part_doc_off, const int64_t* d_part_seed,
-                                    int64_t n_part, lddl_pairs** out, int64_t* head) {
+// lddl_pairs_plan_head (span = nullptr) and lddl_pairs_plan_head_span
+static int plan_head(lddl_ctx* c, void* stream, const lddl_pair_params* prm, const int64_t* d_sent_off,
+                     const int32_t* d_ids, const int32_t* d_sent_len, int64_t n_sent,
+                     const int64_t* d_doc_sent_off, int64_t n_doc, const int64_t* d_part_doc_off,
+                     const int64_t* d_part_seed, int64_t n_part, lddl_pairs** out, int64_t* head,
+                     const lddl_span_params* span) {
   if (out) *out = nullptr;
   PlanKnobs knobs;
   int rc;
   if (!out) LDDL_FAIL(-1, "null argument");
-  if ((rc = check_plan_args(c, prm, &knobs))) return rc;
+  if ((rc = check_plan_args(c, prm, span, &knobs))) return rc;
   hipStream_t st = as_stream(stream);
   // until it is handed out, an error return drops the plan: its blocks go back on `st` (after
   // the tail launch, when one is in flight)
@@ -199,6 +215,10 @@ extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_p
   P->cls_id = c->tab.special_id[kCls];
   P->sep_id = c->tab.special_id[kSep];
   P->max_pred = max_predictions(prm);
+  if (span) {
+    P->span = true;
+    P->span_prm = *span;
+  }
   LDDL_HIP(hipEventCreate(&P->ev[0]));
   LDDL_HIP(hipEventCreate(&P->ev[1]));
   P->work.reset(new PlanWork(c, &P->prm, d_ids, d_part_seed, n_sent, n_part, st, P->mem, knobs));
@@ -219,6 +239,27 @@ extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_p
   }
   *out = P.release();
   return 0;
+}
+
+extern "C" int lddl_pairs_plan_head(lddl_ctx* c, void* stream, const lddl_pair_params* prm,
+                                    const int64_t* d_sent_off, const int32_t* d_ids,
+                                    const int32_t* d_sent_len, int64_t n_sent,
+                                    const int64_t* d_doc_sent_off, int64_t n_doc,
+                                    const int64_t* d_part_doc_off, const int64_t* d_part_seed,
+                                    int64_t n_part, lddl_pairs** out, int64_t* head) {
+  return plan_head(c, stream, prm, d_sent_off, d_ids, d_sent_len, n_sent, d_doc_sent_off, n_doc,
+                   d_part_doc_off, d_part_seed, n_part, out, head, nullptr);
+}
+
+extern "C" int lddl_pairs_plan_head_span(lddl_ctx* c, void* stream, const lddl_pair_params* prm,
+                                         const int64_t* d_sent_off, const int32_t* d_ids,
+                                         const int32_t* d_sent_len, int64_t n_sent,
+                                         const int64_t* d_doc_sent_off, int64_t n_doc,
+                                         const int64_t* d_part_doc_off, const int64_t* d_part_seed,
+                                         int64_t n_part, lddl_pairs** out, int64_t* head,
+                                         const lddl_span_params* span) {
+  return plan_head(c, stream, prm, d_sent_off, d_ids, d_sent_len, n_sent, d_doc_sent_off, n_doc,
+                   d_part_doc_off, d_part_seed, n_part, out, head, span);
 }
 
 extern "C" int lddl_pairs_plan_tail(lddl_pairs* P, int64_t* counts, int32_t* head_valid) {

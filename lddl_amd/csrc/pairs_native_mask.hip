@@ -1,7 +1,7 @@
 // Pair stage, the native planner's masking (LDDL_RNG_NATIVE; the stage's other units: file map in
-// pairs_api.hip): mask_native_kernel (plain) and mask_ww_native_kernel (whole word) with their
-// wave helpers, and the one host function that launches whichever applies, in the shape that
-// native_shape.h gives.
+// pairs_api.hip): mask_native_kernel (plain), mask_ww_native_kernel (whole word) and
+// mask_span_native_kernel (n-gram) with their wave helpers, and the one host function that
+// launches whichever applies, in the shape that native_shape.h gives.
 #include "collate_dev.h"  // ContBits, cont_id
 #include "native_dev.h"
 #include "native_shape.h"
@@ -241,13 +241,165 @@ __global__ void __launch_bounds__(256) mask_ww_native_kernel(NativeArgs A, ContB
   if (lane == 0) A.nmask[q] = base;
 }
 
+// ---------------------------------------------------------------------------------------------
+// N-gram (span) static masking (lddl_pairs_plan_head_span): the budgeted n-gram walk
+// of Megatron-LM's BERT dataset and ALBERT on the whole-word path's words, streams and visiting
+// order. A start draws a length in words, the n-gram shrinks until its tokens fit what is left of
+// the budget, and a start whose n-gram touches a word already taken is dropped. Native RNG only.
+// ---------------------------------------------------------------------------------------------
+
+// cum[k - 1] = P(len <= k) of lddl_span_params, by value (the compares run on scalar registers)
+struct SpanCum {
+  float cum[LDDL_SPAN_MAX_N - 1];
+};
+
+// bits [lo, hi) of a 64-bit word, 0 <= lo < hi <= 64
+__device__ inline uint64_t bit_range(int32_t lo, int32_t hi) {
+  return (hi - lo == 64 ? ~0ull : (1ull << (hi - lo)) - 1) << lo;
+}
+
+// One wave per pair, lane = token of a 64-token window; budget, pool and write-back as
+// mask_ww_native_kernel. LDS per wave: the entries kk[seqp] and the word table tab[W + 1].
+//  1. as the whole-word kernel's: tokens loaded coalesced, the ballots of specials and of heads
+//     per window, one Philox block per head. A head's word index is the heads before its window
+//     (wave-uniform, carried) + the heads below its lane; the non-special tokens before it are
+//     counted the same way. Its entry is key << 32 | word << 16 | L, L the length drawn from the
+//     block's second word, in the lane's LDS column; tab[word] = head | tokens before << 16,
+//     tab[W] = n | all non-special tokens << 16. So tok(j, n) = (tab[j + n] >> 16) - (tab[j] >> 16)
+//     and the tokens of an n-gram are [head(j), head(j + n)) without the specials. The entry
+//     carries the word index and the head is read from the table (one broadcast LDS read that
+//     the walk needs anyway, for the tokens before the word). The special ballot of window w
+//     stays in lane w's registers.
+//  2. the select-min of the whole-word walk names the next start j and its L. Lanes 0 .. 15 each
+//     test one length n = lane + 1 (one LDS read of tab[min(j + n, W)], one compare with the
+//     budget left); the ballot, cut at min(L, W - j), is a prefix of the lanes and its last set
+//     bit the largest n that fits: no serial shrink. Lane w holds the covered bits of words
+//     64 w .. 64 w + 63: the overlap test is the n-gram's word range ANDed with them and one
+//     ballot (a covered start fails it too, so step 2 of the definition needs no test of its
+//     own), covering an OR of the same range. Lane w then ORs its part of the token range,
+//     without its window's specials, into the masked bits of window w.
+//  3. the whole-word kernel's output phase; the masked bits go through the entries' LDS.
+// Every cross-lane step is reached by all 64 lanes; j, L, the fitting n and the budget left are
+// wave-uniform (readlane / ballots), so every branch on them is one.
+__global__ void __launch_bounds__(256) mask_span_native_kernel(NativeArgs A, ContBits C, SpanCum S,
+                                                               int32_t seqp) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_sp[];
+  const int w = wave_id(), lane = threadIdx.x & 63, nwv = blockDim.x >> 6;
+  const int64_t q = (int64_t)blockIdx.x * nwv + w;
+  if (q >= A.n_pairs) return;
+  uint64_t* kk = reinterpret_cast<uint64_t*>(s_sp + (size_t)w * ((size_t)12 * seqp + 8));  // [seqp]
+  uint32_t* tab = reinterpret_cast<uint32_t*>(kk + seqp);                                 // [seqp + 2]
+  const PairDesc d = A.desc[q];
+  const int32_t na = __builtin_amdgcn_readfirstlane(d.na);
+  const int32_t n = __builtin_amdgcn_readfirstlane(min(d.na + (d.nb_rn & 0x7FFFFFFF), seqp));
+  const int32_t nwin = (n + 63) >> 6;
+  const int32_t budget = __builtin_amdgcn_readfirstlane(A.nmask[q]);
+  const int64_t p = A.ppart[q];
+  const uint64_t key = part_key(A.native_seed, A.part_seed[p]);
+  const int64_t idx = q - A.part_base[p];
+  const int64_t a0 = A.kscan[d.a_ks] + d.a_front, b0 = A.kscan[d.b_ks] + d.b_front - na;
+  bool carry = false;  // the token before the window is a literal special
+  uint64_t cand = 0;   // bit wi: token wi * 64 + lane is a head not yet visited
+  uint64_t spw = 0;    // lane wi: the special ballot of window wi
+  int32_t words = 0, toks = 0;  // heads / non-special tokens before the window (wave-uniform)
+  for (int32_t wi = 0; wi < nwin; ++wi) {
+    const int32_t t = wi * 64 + lane;
+    const bool in = t < n;
+    const int32_t id = in ? A.dense.ld((t < na ? a0 : b0) + t) : 0;
+    const bool special = in && (id == A.cls_id || id == A.sep_id);
+    const uint64_t sp = ballot(special);
+    const bool prev_special = lane ? ((sp >> (lane - 1)) & 1) != 0 : carry;
+    carry = (sp >> 63) != 0;
+    const bool cont = in && !special && t != 0 && t != na && !prev_special && cont_id(C, id);
+    const bool head = in && !special && !cont;
+    const uint64_t hb = ballot(head), ns = ballot(in && !special);
+    spw = lane == wi ? sp : spw;
+    if (head) {
+      CtrRng r = token_rng(key, idx, kStreamWordKey, t);
+      const uint32_t x = r.u32();
+      const float u = u01(r.u32());
+      uint32_t len = 1;
+#pragma unroll
+      for (int k = 0; k < LDDL_SPAN_MAX_N - 1; ++k) len += u >= S.cum[k] ? 1u : 0u;
+      const uint32_t word = (uint32_t)words + popc_below(hb);
+      kk[t] = ((uint64_t)x << 32) | ((uint64_t)word << 16) | len;
+      tab[word] = (uint32_t)t | ((uint32_t)toks + popc_below(ns)) << 16;
+      cand |= 1ull << wi;
+    }
+    words += __popcll(hb);
+    toks += __popcll(ns);
+  }
+  const int32_t W = words;
+  if (lane == 0) tab[W] = (uint32_t)n | (uint32_t)toks << 16;
+  wave_sync();
+  uint64_t best = column_min(kk, cand, lane);
+  uint64_t cov = 0;  // lane wi: covered words 64 wi .. 64 wi + 63
+  uint64_t mb = 0;   // lane wi: masked tokens of window wi
+  int32_t masked = 0;
+  const int32_t cl = lane < LDDL_SPAN_MAX_N ? lane : LDDL_SPAN_MAX_N - 1;
+  while (masked < budget) {
+    const uint32_t kmin = wave_min_u32((uint32_t)(best >> 32));
+    const uint64_t win = ballot(cand != 0 && (uint32_t)(best >> 32) == kmin);
+    if (!win) break;  // every word visited
+    const int wl = __ffsll((unsigned long long)win) - 1;
+    const uint32_t sel = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)best, wl);
+    const int32_t j = (int32_t)(sel >> 16), nmax = min((int32_t)(sel & 0xFFFF), W - j);
+    const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tab[j]);
+    const uint32_t e = tab[min(j + cl + 1, W)];  // lane < 16: the table past n = lane + 1 words
+    const int32_t h0 = (int32_t)(e0 & 0xFFFF), t0 = (int32_t)(e0 >> 16);
+    const uint64_t fit = ballot(lane < nmax && (int32_t)(e >> 16) - t0 <= budget - masked);
+    if (fit) {
+      const int32_t nf = 64 - __clzll((long long)fit);  // the largest n that fits
+      const int32_t wlo = max(j - 64 * lane, 0), whi = min(j + nf - 64 * lane, 64);
+      const uint64_t wr = wlo < whi ? bit_range(wlo, whi) : 0ull;
+      if (!ballot((wr & cov) != 0)) {
+        cov |= wr;
+        const uint32_t e1 = (uint32_t)__builtin_amdgcn_readlane((int)e, nf - 1);
+        masked += (int32_t)(e1 >> 16) - t0;
+        const int32_t lo = max(h0 - 64 * lane, 0), hi = min((int32_t)(e1 & 0xFFFF) - 64 * lane, 64);
+        if (lo < hi) mb |= bit_range(lo, hi) & ~spw;
+      }
+    }
+    if (lane == wl) {
+      cand &= ~(1ull << (h0 >> 6));
+      best = column_min(kk, cand, lane);
+    }
+  }
+  wave_sync();  // (the entries are read; their first slots take the masked bits)
+  if (lane < nwin) kk[lane] = mb;
+  wave_sync();
+  const int64_t m0 = A.moff[q];
+  int32_t base = 0;
+  for (int32_t wi = 0; wi < nwin; ++wi) {
+    const uint64_t m = kk[wi];
+    if ((m >> lane) & 1) {
+      const int32_t t = wi * 64 + lane;
+      const int64_t at = m0 + base + (int32_t)popc_below(m);
+      CtrRng drng = token_rng(key, idx, kStreamWordDecide, t);
+      const uint32_t x = drng.u32(), y = drng.u32();
+      A.mpos[at] = (uint16_t)(t < na ? t + 1 : t + 2);
+      A.mtok[at] = x < kNat80 ? A.mask_id
+                   : x < kNat90 ? kKeep
+                                : (int32_t)lemire_below(y, (uint32_t)A.vocab_size, drng);
+    }
+    base += __popcll(m);
+  }
+  if (lane == 0) A.nmask[q] = base;
+}
+
 }  // namespace
 
 void launch_native_masks(const lddl_pairs* P, const PlanWork& W, NativeArgs& A) {
   const MaskShape m = native_mask_shape(W.prm->seq, P->max_pred);
   A.words = m.words;
   if (!A.n_pairs) return;
-  if (!W.prm->whole_word) {
+  if (P->span) {  // (check_plan_args: the shape fits; whole_word beside it changes nothing)
+    const SpanShape s = native_span_shape(W.prm->seq);
+    SpanCum cum;
+    for (int k = 0; k < LDDL_SPAN_MAX_N - 1; ++k) cum.cum[k] = P->span_prm.cum[k];
+    hipLaunchKernelGGL(mask_span_native_kernel, dim3(s.grid(A.n_pairs)), dim3(s.threads()), s.lds_bytes(),
+                       W.st, A, ContBits{W.c->d_cont_bits, W.c->vocab_size}, cum, s.seqp);
+  } else if (!W.prm->whole_word) {
     hipLaunchKernelGGL(mask_native_kernel, dim3(m.grid(A.n_pairs)), dim3(m.threads()), m.lds_bytes(), W.st,
                        A, m.stage_cap, m.ppw);
   } else {

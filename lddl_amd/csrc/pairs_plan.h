@@ -239,6 +239,8 @@ struct lddl_pairs {
   bool tail_pending = false;
   bool head_valid = false;  // the head range's tables (and what was gathered from them) stand
   lddl_pair_params prm{};
+  bool span = false;            // n-gram static masking (lddl_pairs_plan_head_span), with
+  lddl_span_params span_prm{};  // the caller's params, checked
   std::unique_ptr<lddl::PlanWork> work;  // between the head and the tail call
 
   lddl_pairs(lddl::DevArena* arena, hipStream_t stream) : mem(arena, stream), st(stream) {}

@@ -41,7 +41,8 @@ def make_batch_pairs(ctx, args, partitions, corpus, timer=None):
                     seq=args.target_seq_length, dup=args.duplicate_factor, masking=args.masking,
                     short_seq_prob=args.short_seq_prob, masked_lm_ratio=args.masked_lm_ratio,
                     rng=getattr(args, 'rng', 'replay'), native_seed=args.seed,
-                    whole_word=getattr(args, 'whole_word_masking', False))
+                    whole_word=getattr(args, 'whole_word_masking', False),
+                    span=getattr(args, 'ngram_masking', None))
     tm('pairs')
     return pb
 

@@ -154,6 +154,24 @@ def _run_gpu_workers(args, n_workers, vocab, ctx0, batch_it, outdir, pool, copie
         timer.acc['gpu_workers'] = n_workers
 
 
+def parse_ngram_spec(spec):
+    """--ngram-masking SPEC -> the `span=` value of make_pairs: 'N' -> int, 'p1,p2,...' -> a list
+    of probabilities, checked by lddl_amd.torch.span (ValueError)."""
+    from ...torch.span import parse
+    if isinstance(spec, str):
+        parts = [x.strip() for x in spec.split(',')]
+        try:
+            spec = int(parts[0]) if len(parts) == 1 else [float(x) for x in parts]
+        except ValueError:
+            raise ValueError('--ngram-masking: N or a comma-separated list of probabilities, '
+                             'not {!r}'.format(spec)) from None
+    try:
+        parse(spec)
+    except ValueError as e:
+        raise ValueError('--ngram-masking: {}'.format(e)) from None
+    return spec  # (the plain value: args travel to worker processes)
+
+
 def main(args):
     if args.bin_size is not None:
         if args.bin_size > args.target_seq_length:
@@ -172,6 +190,12 @@ def main(args):
         raise ValueError('--whole-word-masking needs --masking and --rng native (replay '
                          'reproduces the reference, which has no whole-word masking; without '
                          '--masking the loaders mask: whole_word_masking=True there)')
+    if getattr(args, 'ngram_masking', None) is not None:
+        if not (args.masking and getattr(args, 'rng', 'replay') == 'native'):
+            raise ValueError('--ngram-masking needs --masking and --rng native (replay reproduces '
+                             'the reference, which has no n-gram masking; without --masking the '
+                             'loaders mask)')
+        args.ngram_masking = parse_ngram_spec(args.ngram_masking)
     world =int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -374,6 +398,11 @@ def attach_args(parser=None):
                     help_str='lddl_amd, with --masking and --rng native: mask whole words '
                     "(Google BERT's do_whole_word_mask); a pair gets at most the per-token "
                     "mode's number of masked positions")
+    parser.add_argument('--ngram-masking', type=str, default=None, metavar='SPEC',
+                        help='lddl_amd, with --masking and --rng native: mask n-grams of whole '
+                        'words within the per-token budget (Megatron-LM BERT, ALBERT, SpanBERT). '
+                        'SPEC: N (lengths 1..N, weights 1/n) or comma-separated probabilities of '
+                        'the lengths 1, 2, ... (at most 16). Default: off')
     parser.add_argument('--gpu-batch-bytes', type=int, default=512 << 20,
                         help='lddl_amd: input text bytes per GPU batch of partitions (bounds HBM '
                              'use; consecutive batches overlap their GPU work, rendering and file '

@@ -103,9 +103,26 @@ def _check_whole_word(whole_word, masking, rng):
                          'reference, which has no whole-word masking)')
 
 
+def _check_span(span, masking, rng):
+    """`span` parsed (None or a SpanMasking; lddl_amd.torch.span owns the value's format);
+    ValueError for a malformed value and for the combinations the planner refuses."""
+    if span is None:
+        return None
+    from .torch.span import parse
+    span = parse(span)
+    if not masking:
+        raise ValueError('span needs masking=True (without static masking the loaders mask: '
+                         'span= there)')
+    if rng != 'native':
+        raise ValueError("span needs rng='native' (the replay mode reproduces the reference, "
+                         'which has no n-gram masking)')
+    return span
+
+
 def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_seed, seq=128,
                dup=5, masking=False, short_seq_prob=0.1, masked_lm_ratio=0.15, rng='replay',
-               native_seed=12345, _capacity_scale=1.0, _trace=None, *, whole_word=False):
+               native_seed=12345, _capacity_scale=1.0, _trace=None, *, whole_word=False,
+               span=None):
     """All inputs are cuda tensors (int64 offsets / seeds; tokenizer output from Context.tokenize).
 
     rng='replay' reproduces CPython `random` after random.seed(part_seed[p]) per partition.
@@ -113,6 +130,12 @@ def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_se
     whole_word=True (with masking=True and rng='native' only) masks whole words, as Google BERT's
     do_whole_word_mask: the same pairs as whole_word=False, each with at most the per-token
     mode's number of masked positions, possibly none.
+
+    span=N or a list of probabilities (the value of lddl_amd.torch.span; with masking=True and
+    rng='native' only) masks n-grams of whole words within the same budget, as Megatron-LM's BERT
+    dataset and ALBERT do: a start draws a length, the n-gram shrinks until it fits what is left
+    of the budget, and a start that touches a word already taken is dropped. span=1
+    is whole_word=True; whole_word beside span changes nothing.
 
     A replay batch of more partitions than the device holds planner waves is planned
     time-sliced in one range (LDDL_PLAN_SLICE, include/lddl_amd.h). With LDDL_PLAN_SPLIT forced,
@@ -124,6 +147,7 @@ def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_se
     LDDL_PLAN_SLICE.)
     """
     _check_whole_word(whole_word, masking, rng)
+    span = _check_span(span, masking, rng)
     dev = ctx.device
     prm = PairParams(seq, dup, int(bool(masking)), RNG_REPLAY if rng == 'replay' else RNG_NATIVE,
                      short_seq_prob, masked_lm_ratio, native_seed, int(bool(whole_word)))
@@ -135,10 +159,13 @@ def make_pairs(ctx, sent_off, ids, sent_len, doc_sent_off, part_doc_off, part_se
     head = np.zeros(8, np.int64)
     head_valid = ctypes.c_int32(0)
     st = _stream()
-    check(lib.lddl_pairs_plan_head(ctx.handle, st, ctypes.byref(prm), _ptr(sent_off), _ptr(ids),
-                                   _ptr(sent_len), n_sent, _ptr(doc_sent_off), n_doc,
-                                   _ptr(part_doc_off), _ptr(part_seed), n_part, ctypes.byref(h),
-                                   head.ctypes.data))
+    plan_args = (ctx.handle, st, ctypes.byref(prm), _ptr(sent_off), _ptr(ids), _ptr(sent_len),
+                 n_sent, _ptr(doc_sent_off), n_doc, _ptr(part_doc_off), _ptr(part_seed), n_part,
+                 ctypes.byref(h), head.ctypes.data)
+    if span is None:
+        check(lib.lddl_pairs_plan_head(*plan_args))
+    else:
+        check(lib.lddl_pairs_plan_head_span(*plan_args, span.ptr(masked_lm_ratio)))
     try:
         o = None
         caps = (0, 0, 0)
@@ -199,7 +226,7 @@ def _side_stream(dev):
 
 def tokenize_and_pair_chunked(ctx, text, sent_off, doc_sent_off, part_doc_off, part_seed,
                               n_chunks=2, max_pieces=512, tok_stream=None, whole_word=False,
-                              **pair_kw):
+                              *, span=None, **pair_kw):
     """tokenize + make_pairs over `n_chunks` partition-aligned chunks, pipelined on two streams:
     every chunk's tokenizer is queued on a side stream, each chunk's pair planner on the current
     stream waits only for its own chunk's tokens, so chunk k+1 is tokenized while chunk k is
@@ -207,6 +234,7 @@ def tokenize_and_pair_chunked(ctx, text, sent_off, doc_sent_off, part_doc_off, p
     bit-identical to one call over all partitions. Returns the chunks' PairBatch list in
     partition order."""
     _check_whole_word(whole_word, pair_kw.get('masking', False), pair_kw.get('rng', 'replay'))
+    span = _check_span(span, pair_kw.get('masking', False), pair_kw.get('rng', 'replay'))
     n_part = part_doc_off.numel() - 1
     cuts = [round(k * n_part / n_chunks) for k in range(n_chunks + 1)]
     pc = torch.tensor(cuts, dtype=torch.int64, device=part_doc_off.device)
@@ -233,7 +261,8 @@ def tokenize_and_pair_chunked(ctx, text, sent_off, doc_sent_off, part_doc_off, p
             x.record_stream(main)
         pb = make_pairs(ctx, so, ids, sl, doc_sent_off[d_cut[k]:d_cut[k + 1] + 1] - s_cut[k],
                         part_doc_off[cuts[k]:cuts[k + 1] + 1] - d_cut[k],
-                        part_seed[cuts[k]:cuts[k + 1]], whole_word=whole_word, **pair_kw)
+                        part_seed[cuts[k]:cuts[k + 1]], whole_word=whole_word, span=span,
+                        **pair_kw)
         del ids
         out.append(pb)
     return out

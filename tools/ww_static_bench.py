@@ -1,14 +1,15 @@
-"""Time the native-RNG pair planner with static masking, per-token and whole-word
-(`make_pairs(..., rng='native', masking=True, whole_word=...)`), on one synthetic corpus that
-stays resident on the GPU, the two alternating call by call.
+"""Time the native-RNG pair planner with static masking, per-token, whole-word and n-gram
+(`make_pairs(..., rng='native', masking=True, whole_word=... / span=3)`), on one synthetic corpus
+that stays resident on the GPU, the variants alternating call by call.
 
 The figure is `PairBatch.plan_ms`: HIP events from the planner's first launch to the end of its
 last kernel, which on the native path spans the walk (count and emit pass), the mask stage and
-the order kernel; the two variants differ in the mask stage only. Per sequence length and
+the order kernel; the variants differ in the mask stage only. Per sequence length and
 variant: `--reps` timed calls after `--warmup` untimed ones; the line gives the median, min and
 max over the calls (the spread within the run) and the pairs and masked positions of a call. On a
 tree without whole-word static masking (no `whole_word` keyword of make_pairs) only the
-per-token path is timed, so the same script measures a parent commit. Prints one JSON line and,
+per-token path is timed, and without the `span` keyword no n-gram variant (N = 3, weights 1 / n),
+so the same script measures a parent commit. Prints one JSON line and,
 with `--out`, writes it to that file.
 
     python tools/ww_static_bench.py [--mib 256] [--part-kib 1024] [--seqs 128 512] [--reps 15]
@@ -57,6 +58,8 @@ def main():
     d_seed = torch.arange(len(part) - 1, dtype=torch.int64, device=dev) * 7919 + 12345
     has_ww = 'whole_word' in inspect.signature(make_pairs).parameters and not a.per_token_only
     variants = [('per_token', {})] + ([('whole_word', {'whole_word': True})] if has_ww else [])
+    if has_ww and 'span' in inspect.signature(make_pairs).parameters:
+        variants.append(('span3', {'span': 3}))
     res = {'build_id': lib.lddl_build_id().decode(), 'device': torch.cuda.get_device_name(0),
            'corpus_mib': a.mib, 'partitions': len(part) - 1, 'dup': 5, 'reps': a.reps,
            'warmup': a.warmup, 'plan_ms': {}}
