@@ -809,6 +809,77 @@ int lddl_mlm_compact_flat(void* stream, const int64_t* d_labels, int64_t R, int6
                           int64_t ignore_index, int64_t capacity, int64_t* d_flat_positions,
                           int64_t* d_flat_ids, int32_t* d_num_masked, int64_t* d_total);
 
+/* ---------------------------------------------------------------------------------------------
+ * BART denoising (past the reference): sentence permutation and text infilling of
+ * tokenized documents, one launch per batch, asynchronous on `stream`, no temporaries, no host
+ * wait. The input is lddl_tokenize's output read in place: sentence s holds
+ * d_sent_len[s] & (2^30 - 1) pieces from d_ids[d_sent_off[s]]; document (= sample) d holds the
+ * sentences d_doc_sent_off[d] .. d_doc_sent_off[d + 1]; output row i is sample d_rows[i], or i
+ * with d_rows NULL. int64 [batch, seq_len] d_input_ids, d_attention_mask, d_decoder_input_ids
+ * and d_labels and int32 [batch] d_src_lengths are written in full. L = seq_len, per row i:
+ *   budget   the sample keeps its first T = L - 2 pieces in original order: the sentence that
+ *     crosses T is cut and the sentences after it have length 0;
+ *   units    sentence u < LDDL_DENOISE_MAX_UNITS - 1 is unit u; the sentences from
+ *     LDDL_DENOISE_MAX_UNITS - 1 on are one tail unit and keep their order inside it;
+ *   sentence permutation   rs(u) = Philox4x32-10 at flat index i * draw_stride + u (the
+ *     collates' counter layout: flat low, flat high, counter low, counter high) under the key
+ *     seed ^ LDDL_DENOISE_SENT_XOR; a unit of non-zero length takes part iff
+ *     u01(rs(u).x) < permute_p (u01(v) = (v >> 8) * 2^-24); the participants sorted by
+ *     (rs(u).y, u) fill the participants' places in order, every other unit stays;
+ *   words    over the permuted sequence, slot x is a head iff it is the first piece of a
+ *     sentence or its id is no continuation ("##x") id; word(x) = the heads at or before x, - 1;
+ *   spans    r(x) = the same Philox call at flat index i * draw_stride + x under the key seed; a
+ *     head of word j starts a span iff u01(r.x) < p_start; its length is
+ *     len = #{k in [0, n) : u01(r2.x) >= cum[k]}, r2 the call at the same index under the key
+ *     seed ^ LDDL_SPAN_SEED_XOR; e(j) = j + len for a starting word, else 0; E(j) = the maximum
+ *     of e over the words before j;
+ *   emission   a slot of word j: nothing if E(j) > j (the run already has its noise token);
+ *     else, if the word starts a span of len >= 1, its head gives one noise token and its
+ *     continuations nothing; else, if it starts one of len = 0, its head gives a noise token
+ *     and then its id, its continuations their ids; else its id. The noise token is
+ *     (r.w * vocab_len) >> 32 if u01(r.y) < random_ratio, else mask_id;
+ *   rows     input_ids = bos, the emitted ids, eos, then pad; src_lengths = the emitted count
+ *     + 2, untruncated: beyond L the ids at destinations >= L - 1 are dropped and eos sits at
+ *     L - 1; attention_mask = 1 up to and including eos; labels = bos, the budgeted pieces in
+ *     original order, eos, then ignore_index; decoder_input_ids = decoder_start_id, then labels
+ *     one slot to the right, pad where that label is ignored.
+ * permute_p = 0 is the identity; p_start = 0 leaves the permuted sample.
+ *
+ * lddl_denoise_params_make (host only): P(len = k) proportional to weights[k], k = 0 .. n (n + 1
+ * entries; NULL: Poisson(3) on 0 .. n, the default being n = 10); cum[k] = float(P(len <= k))
+ * for k < n and 1 from there on; p_start solves 1 - prod_{k < n} (1 - s * P(len > k)) =
+ * mask_ratio, the probability that a word deep in a row is deleted or replaced (inserted noise
+ * tokens do not count), by lddl_span_params_make's bisection. Fails with -1 on n outside
+ * [1, LDDL_SPAN_MAX_N], a negative, non-finite or all-zero weight list, mask_ratio outside
+ * [0, 1] or above what p_start = 1 reaches, or out NULL.
+ *
+ * lddl_bart_denoise fails with -1 before anything is launched on a NULL ctx, params NULL or not
+ * such as lddl_denoise_params_make writes (n, p_start in [0, 1], cum rising within [0, 1] below
+ * n and 1 from n on), seq_len < 2 or > 2^24, draw_stride < seq_len, permute_p or random_ratio
+ * outside [0, 1], vocab_len outside [1, 2^32], and, with batch > 0, a NULL table or output.
+ * batch <= 0 returns 0 and launches nothing. The row indices are the caller's to check.
+ * ------------------------------------------------------------------------------------------- */
+#define LDDL_DENOISE_MAX_UNITS 256
+#define LDDL_DENOISE_SENT_XOR 0xD1B54A32D192ED03ull
+typedef struct {
+  int32_t n;                   /* longest span, in words */
+  float p_start;               /* a head starts a span with this probability */
+  float cum[LDDL_SPAN_MAX_N];  /* cum[k] = P(len <= k) for k < n, 1 from there on */
+} lddl_denoise_params;
+
+int lddl_denoise_params_make(double mask_ratio, int32_t n, const double* weights,
+                             lddl_denoise_params* out);
+
+int lddl_bart_denoise(lddl_ctx* ctx, void* stream, const int32_t* d_ids,
+                      const int64_t* d_sent_off, const int32_t* d_sent_len,
+                      const int64_t* d_doc_sent_off, const int64_t* d_rows, int32_t batch,
+                      int32_t seq_len, int64_t* d_input_ids, int64_t* d_attention_mask,
+                      int64_t* d_decoder_input_ids, int64_t* d_labels, int32_t* d_src_lengths,
+                      int64_t bos_id, int64_t eos_id, int64_t pad_id, int64_t mask_id,
+                      int64_t decoder_start_id, int64_t ignore_index, int64_t vocab_len,
+                      uint64_t seed, uint64_t counter, int32_t draw_stride, float permute_p,
+                      float random_ratio, const lddl_denoise_params* params);
+
 #ifdef __cplusplus
 }
 #endif

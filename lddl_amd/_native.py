@@ -155,6 +155,12 @@ SIGNATURES = {
                                              c_vp, c_vp]),
     'lddl_mlm_compact_flat': (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                              c_vp, c_vp]),
+    # BART denoising: a const lddl_denoise_params* (DenoiseParams below) comes last
+    'lddl_denoise_params_make': (ctypes.c_int, [c_dbl, c_i32, c_vp, c_vp]),
+    'lddl_bart_denoise': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                         c_i64, c_i64, c_i64, c_u64, c_u64, c_i32, ctypes.c_float,
+                                         ctypes.c_float, c_vp]),
 }
 
 
@@ -174,6 +180,12 @@ class SpanParams(ctypes.Structure):
     """lddl_span_params (include/lddl_amd.h)."""
     _fields_ = [('n', ctypes.c_int32), ('p_start', ctypes.c_float),
                 ('cum', ctypes.c_float * (SPAN_MAX_N - 1))]
+
+
+class DenoiseParams(ctypes.Structure):
+    """lddl_denoise_params (include/lddl_amd.h)."""
+    _fields_ = [('n', ctypes.c_int32), ('p_start', ctypes.c_float),
+                ('cum', ctypes.c_float * SPAN_MAX_N)]
 
 
 RNG_REPLAY, RNG_NATIVE = 0, 1

@@ -3,16 +3,9 @@
 // start probability at which a word deep in a row is masked with probability mlm_probability.
 #include "common.h"
 #include "lddl_amd.h"
+#include "span_solve.h"
 
 #include <cmath>
-
-// P(word j is covered) for a word with n - 1 words before it: the span of the word k places back
-// covers it iff it started (s) and is longer than k (q_k); the starts are independent.
-static double span_coverage(double s, const double* q, int n) {
-  double miss = 1.0;
-  for (int k = 0; k < n; ++k) miss *= 1.0 - s * q[k];
-  return 1.0 - miss;
-}
 
 extern "C" int lddl_span_params_make(double mlm_probability, int32_t n, const double* weights,
                                      lddl_span_params* out) {
@@ -48,12 +41,6 @@ extern "C" int lddl_span_params_make(double mlm_probability, int32_t n, const do
     return 0;
   }
   // the coverage rises strictly with s (q[0] = 1) from 0 at s = 0 to 1 at s = 1
-  double lo = 0.0, hi = 1.0;
-  for (int it = 0; it < 200; ++it) {
-    const double mid = 0.5 * (lo + hi);
-    if (mid <= lo || mid >= hi) break;
-    (span_coverage(mid, q, n) < mlm_probability ? lo : hi) = mid;
-  }
-  out->p_start = (float)(0.5 * (lo + hi));
+  out->p_start = (float)lddl::span_solve_start(mlm_probability, q, n);
   return 0;
 }

@@ -4,7 +4,8 @@
 the reference) and the online loaders (`get_bert_pretrain_online_data_loader`, `collate_pairs`:
 raw text to batches without shards; `get_bert_pretrain_online_packed_data_loader`: the same with
 sequence packing planned and collated on the device; both past the reference) and the compact
-MLM targets (`compact_labels`, `CompactMLMTargets`: a `collate_fn` for every loader) are resolved
+MLM targets (`compact_labels`, `CompactMLMTargets`: a `collate_fn` for every loader) and BART
+denoising (`bart_denoise`, `get_bart_pretrain_data_loader`; past the reference) are resolved
 lazily, so that DataLoader workers started with `spawn` / `forkserver` import only the
 worker-side modules (`packing`, `seqpack`, `datasets`), never the native library."""
 
@@ -21,4 +22,7 @@ def __getattr__(name):
     if name in ('compact_labels', 'CompactMLMTargets'):
         from . import targets
         return getattr(targets, name)
+    if name in ('bart_denoise', 'get_bart_pretrain_data_loader'):
+        from . import denoise
+        return getattr(denoise, name)
     raise AttributeError(name)
