@@ -879,6 +879,97 @@ int lddl_bart_denoise(lddl_ctx* ctx, void* stream, const int32_t* d_ids,
                       int64_t decoder_start_id, int64_t ignore_index, int64_t vocab_len,
                       uint64_t seed, uint64_t counter, int32_t draw_stride, float permute_p,
                       float random_ratio, const lddl_denoise_params* params);
+/* The same launch with the continuation bitmap handed in (bit id of word id >> 5 set: id
+ * continues a word; ids outside [0, n_ids) never do) in place of the context that owns one:
+ * lddl_bpe_cont_bits for a byte-level BPE vocabulary. Refuses what lddl_bart_denoise refuses,
+ * with a NULL bitmap or n_ids outside [1, 2^31) where that one refuses a NULL ctx. */
+int lddl_bart_denoise_bits(const uint32_t* d_cont_bits, int64_t n_ids, void* stream,
+                           const int32_t* d_ids, const int64_t* d_sent_off,
+                           const int32_t* d_sent_len, const int64_t* d_doc_sent_off,
+                           const int64_t* d_rows, int32_t batch, int32_t seq_len,
+                           int64_t* d_input_ids, int64_t* d_attention_mask,
+                           int64_t* d_decoder_input_ids, int64_t* d_labels,
+                           int32_t* d_src_lengths, int64_t bos_id, int64_t eos_id,
+                           int64_t pad_id, int64_t mask_id, int64_t decoder_start_id,
+                           int64_t ignore_index, int64_t vocab_len, uint64_t seed,
+                           uint64_t counter, int32_t draw_stride, float permute_p,
+                           float random_ratio, const lddl_denoise_params* params);
+
+/* ---------------------------------------------------------------------------------------------
+ * Byte-level BPE (GPT-2 / RoBERTa / BART vocabularies; past the reference).
+ * Semantics: GPT-2's encoder.py. Input as lddl_segment_fill lays it out: d_text[n_bytes],
+ * d_sent_off[n_sent + 1] rising from 0 to n_bytes (white space between two sentences belongs to
+ * the left one), d_doc_sent_off[n_doc + 1] (NULL: every sentence is a document of its own).
+ *
+ * Pre-tokens. Per document (the match restarts at a document's first byte and sees nothing
+ * outside the document) the text is cut by
+ *   's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+
+ * with \p{L} = general category L*, \p{N} = N*, \s = the White_Space property (U+0009-000D,
+ * 0020, 0085, 00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000; U+001C-001F are not in it)
+ * and every other character "other", combining marks included. A byte that is no part of a
+ * whole sequence (a lead byte C2-F4 with its 1 to 3 continuation bytes inside the document) is
+ * a character of class "other" by itself. The pattern partitions the text. Stated as a local
+ * rule (csrc/bpe_split.hip): a white-space character starts a pre-token iff no white space
+ * stands before it or a non-space follows it; a non-space starts one after nothing and after
+ * white space other than U+0020, never after U+0020, never inside a contraction that fired,
+ * always right after one, and otherwise iff its class differs from the class before; a
+ * contraction fires at an apostrophe with a letter, a number, white space other than U+0020
+ * or nothing before it.
+ * Merges. A pre-token starts as the base tokens of its bytes. Repeat: of the adjacent pairs
+ * take the one of lowest rank and replace all its occurrences, left to right without overlap,
+ * by the merged token; stop when no adjacent pair has a rank.
+ * The one deviation: a pre-token longer than LDDL_BPE_MAX_WORD bytes is merged in consecutive
+ * slices of LDDL_BPE_MAX_WORD bytes from its first byte (WordPiece's 100-character rule has the
+ * same place). Every pre-token up to that length is exact.
+ * Assignment. A pre-token belongs to the sentence that holds its LAST byte, so the pieces of a
+ * document's sentences, concatenated, are encode(document): " World" after "Hello. " goes to
+ * the second sentence.
+ * Output, lddl_tokenize's layout: sentence s has its pieces at d_ids[d_sent_off[s] ..] and
+ * d_sent_len[s] = min(pieces, max_pieces, bytes of the sentence): the first ones are kept, and
+ * no flag bit is set. The bytes of the sentence bound it because its slots do: a sentence that
+ * takes over the white space before it can hold one piece more than it has bytes when hardly
+ * anything in it merges (sentence "a" after "a ": the pieces " ", "a" in one slot). With a
+ * vocabulary that merges a space into the word after it, this does not come up.
+ *
+ * lddl_bpe_create: class_table = the two-level table that lddl_amd.bpe.load_classes packs
+ * from lddl_amd/assets/bpe_classes.txt (tools/bpe_classes.py; a 32-byte header with the Unicode
+ * version, 4352 uint16 page indices, 64-byte pages of 2-bit classes); token
+ * i is token_bytes[token_off[i] .. token_off[i + 1]) (raw bytes: JSON and GPT-2's byte-to-
+ * unicode map are undone by the caller); merges[n_merges][3] = {left, right, merged} ids in
+ * rank order. Fails with -1 (lddl_last_error) on a malformed class table, a byte value without
+ * a single-byte token, an id outside the vocabulary, an operand that is neither a single-byte
+ * token nor the result of an earlier line, a `merged` whose bytes are not left + right, a pair
+ * that an earlier line has, or 2^26 merges and more. Builds on `device`: the pair table (open
+ * addressing, at most half full), the byte -> id map, the class table, and the continuation
+ * bitmap of lddl_bpe_cont_bits: bit id set iff token id can be reached from bytes (a single-
+ * byte token or a merge result) and its bytes do not start with 0x20 (fairseq's
+ * is_beginning_of_word, negated; special tokens count as beginnings). The pointers of
+ * lddl_bpe_cont_bits live as long as the lddl_bpe.
+ * lddl_bpe_info: unicode_version[3] of the class table; any pointer may be NULL.
+ * lddl_bpe_tokenize: asynchronous on `stream`, no host wait; its temporaries (about 5.5 bytes
+ * per byte of text) come from an arena the lddl_bpe owns and are reused by the next call.
+ * Fails with -1 on a NULL lddl_bpe, a negative size, max_pieces < 1, or, with n_sent > 0, a
+ * NULL array; n_sent = 0 launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define LDDL_BPE_MAX_WORD 1024
+typedef struct lddl_bpe lddl_bpe;
+int lddl_bpe_create(int device, const uint8_t* class_table, int64_t class_len,
+                    const uint8_t* token_bytes, const int64_t* token_off, int64_t n_tokens,
+                    const int32_t* merges, int64_t n_merges, lddl_bpe** out);
+int lddl_bpe_destroy(lddl_bpe* bpe);
+int lddl_bpe_info(const lddl_bpe* bpe, int64_t* n_tokens, int64_t* n_merges,
+                  int32_t* unicode_version, int32_t* max_word);
+int lddl_bpe_cont_bits(const lddl_bpe* bpe, const uint32_t** d_bits, int64_t* n_ids);
+int lddl_bpe_tokenize(lddl_bpe* bpe, void* stream, const uint8_t* d_text, int64_t n_bytes,
+                      const int64_t* d_sent_off, int64_t n_sent, const int64_t* d_doc_sent_off,
+                      int64_t n_doc, int32_t max_pieces, int32_t* d_ids, int32_t* d_sent_len);
+/* Measurement aid: the pre-tokenizer alone on the same input, asynchronous on `stream`.
+ * d_stats (device int64[3]) = the pre-tokens of the text, those of at most 64 bytes that cross
+ * the end of the 64-byte tile they start in, and those longer than 64 bytes: the words that
+ * csrc/bpe_merge.hip serves in its tile pass's second window and in its long pass. */
+int lddl_bpe_pretoken_stats(lddl_bpe* bpe, void* stream, const uint8_t* d_text, int64_t n_bytes,
+                            const int64_t* d_sent_off, int64_t n_sent,
+                            const int64_t* d_doc_sent_off, int64_t n_doc, int64_t* d_stats);
 
 #ifdef __cplusplus
 }

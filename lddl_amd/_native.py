@@ -161,6 +161,21 @@ SIGNATURES = {
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
                                          c_i64, c_i64, c_i64, c_u64, c_u64, c_i32, ctypes.c_float,
                                          ctypes.c_float, c_vp]),
+    # the same with (d_cont_bits, n_ids) in place of the context
+    'lddl_bart_denoise_bits': (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                              c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                              c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_u64,
+                                              c_u64, c_i32, ctypes.c_float, ctypes.c_float, c_vp]),
+    # byte-level BPE (lddl_amd/bpe.py)
+    'lddl_bpe_create': (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64,
+                                       ctypes.POINTER(c_vp)]),
+    'lddl_bpe_destroy': (ctypes.c_int, [c_vp]),
+    'lddl_bpe_info': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'lddl_bpe_cont_bits': (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
+    'lddl_bpe_tokenize': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32,
+                                         c_vp, c_vp]),
+    'lddl_bpe_pretoken_stats': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                               c_vp]),
 }
 
 

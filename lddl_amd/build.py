@@ -48,7 +48,9 @@ BUILD_ID_H = os.path.join(CSRC, 'build_id.h')
 # compiled with them turned off. denoise.hip holds none today (its float work is a handful of
 # compares) and the flag keeps a later edit of the unit from bringing them in; the units from
 # before it keep the flags their kernels were measured with.
-UNIT_FLAGS = {'denoise.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
+_NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
+UNIT_FLAGS = {u: _NO_PACKED_FP32 for u in ('denoise.hip', 'bpe_split.hip', 'bpe_merge.hip',
+                                           'bpe_api.hip')}
 UNIT_FLAGS_ID = repr(sorted(UNIT_FLAGS.items()))
 
 

@@ -240,6 +240,44 @@ using namespace lddl;
 static_assert(kDenoiseUnits == LDDL_DENOISE_MAX_UNITS, "the header's S_max is the kernel's");
 static_assert(kDenoiseMaxN == LDDL_SPAN_MAX_N, "one longest span");
 
+// Both entry points: the values are refused first, whatever the continuation bitmap's owner is;
+// `owner_error` is that owner's refusal (a NULL ctx, a NULL bitmap), reported right after them.
+static int denoise_launch(ContBits cont, const char* owner_error, const char* bitmap_error,
+                          void* stream, const int32_t* d_ids, const int64_t* d_sent_off,
+                          const int32_t* d_sent_len, const int64_t* d_doc_sent_off,
+                          const int64_t* d_rows, int32_t batch, int32_t seq_len,
+                          int64_t* d_input_ids, int64_t* d_attention_mask,
+                          int64_t* d_decoder_input_ids, int64_t* d_labels, int32_t* d_src_lengths,
+                          int64_t bos_id, int64_t eos_id, int64_t pad_id, int64_t mask_id,
+                          int64_t decoder_start_id, int64_t ignore_index, int64_t vocab_len,
+                          uint64_t seed, uint64_t counter, int32_t draw_stride, float permute_p,
+                          float random_ratio, const lddl_denoise_params* params) {
+  DenoiseDraw draw;
+  if (denoise_draw_of(params, seed, &draw)) return -1;
+  if (seq_len < 2 || seq_len > (1 << 24))  // 64 lengths of at most seq_len and a carry: int32
+    LDDL_FAIL(-1, "seq_len %d: a row holds bos and eos at least, and 2^24 slots at most", seq_len);
+  if (draw_stride < seq_len) LDDL_FAIL(-1, "draw_stride %d < seq_len %d", draw_stride, seq_len);
+  if (!(permute_p >= 0.f && permute_p <= 1.f) || !(random_ratio >= 0.f && random_ratio <= 1.f))
+    LDDL_FAIL(-1, "permute_p and random_ratio must lie in [0, 1]");
+  if (vocab_len < 1 || vocab_len > (int64_t)1 << 32) LDDL_FAIL(-1, "vocab_len outside [1, 2^32]");
+  if (owner_error) LDDL_FAIL(-1, "%s", owner_error);
+  if (batch <= 0) return 0;
+  if (!d_ids || !d_sent_off || !d_sent_len || !d_doc_sent_off) LDDL_FAIL(-1, "null token table");
+  if (!d_input_ids || !d_attention_mask || !d_decoder_input_ids || !d_labels || !d_src_lengths)
+    LDDL_FAIL(-1, "null output");
+  if (bitmap_error) LDDL_FAIL(-1, "%s", bitmap_error);
+  const DenoiseArgs A{d_ids, d_sent_off, d_sent_len, d_doc_sent_off, d_rows, batch, seq_len,
+                      draw_stride, d_input_ids, d_attention_mask, d_decoder_input_ids, d_labels,
+                      d_src_lengths, bos_id, eos_id, pad_id, mask_id, decoder_start_id,
+                      ignore_index, vocab_len, seed, seed ^ LDDL_DENOISE_SENT_XOR, counter,
+                      permute_p, random_ratio, cont, draw};
+  const DenoiseShape sh = denoise_shape(batch);
+  hipLaunchKernelGGL(denoise_kernel, dim3(sh.grid), dim3(sh.threads()), sh.lds_bytes(),
+                     as_stream(stream), A);
+  LDDL_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" int lddl_bart_denoise(lddl_ctx* c, void* stream, const int32_t* d_ids,
                                  const int64_t* d_sent_off, const int32_t* d_sent_len,
                                  const int64_t* d_doc_sent_off, const int64_t* d_rows,
@@ -251,29 +289,32 @@ extern "C" int lddl_bart_denoise(lddl_ctx* c, void* stream, const int32_t* d_ids
                                  int64_t vocab_len, uint64_t seed, uint64_t counter,
                                  int32_t draw_stride, float permute_p, float random_ratio,
                                  const lddl_denoise_params* params) {
-  // the values first: they are refused whatever the context is
-  DenoiseDraw draw;
-  if (denoise_draw_of(params, seed, &draw)) return -1;
-  if (seq_len < 2 || seq_len > (1 << 24))  // 64 lengths of at most seq_len and a carry: int32
-    LDDL_FAIL(-1, "seq_len %d: a row holds bos and eos at least, and 2^24 slots at most", seq_len);
-  if (draw_stride < seq_len) LDDL_FAIL(-1, "draw_stride %d < seq_len %d", draw_stride, seq_len);
-  if (!(permute_p >= 0.f && permute_p <= 1.f) || !(random_ratio >= 0.f && random_ratio <= 1.f))
-    LDDL_FAIL(-1, "permute_p and random_ratio must lie in [0, 1]");
-  if (vocab_len < 1 || vocab_len > (int64_t)1 << 32) LDDL_FAIL(-1, "vocab_len outside [1, 2^32]");
-  if (!c) LDDL_FAIL(-1, "null ctx");
-  if (batch <= 0) return 0;
-  if (!d_ids || !d_sent_off || !d_sent_len || !d_doc_sent_off) LDDL_FAIL(-1, "null token table");
-  if (!d_input_ids || !d_attention_mask || !d_decoder_input_ids || !d_labels || !d_src_lengths)
-    LDDL_FAIL(-1, "null output");
-  if (!c->d_cont_bits) LDDL_FAIL(-1, "the context has no continuation bitmap");
-  const DenoiseArgs A{d_ids, d_sent_off, d_sent_len, d_doc_sent_off, d_rows, batch, seq_len,
-                      draw_stride, d_input_ids, d_attention_mask, d_decoder_input_ids, d_labels,
-                      d_src_lengths, bos_id, eos_id, pad_id, mask_id, decoder_start_id,
-                      ignore_index, vocab_len, seed, seed ^ LDDL_DENOISE_SENT_XOR, counter,
-                      permute_p, random_ratio, ContBits{c->d_cont_bits, c->vocab_size}, draw};
-  const DenoiseShape sh = denoise_shape(batch);
-  hipLaunchKernelGGL(denoise_kernel, dim3(sh.grid), dim3(sh.threads()), sh.lds_bytes(),
-                     as_stream(stream), A);
-  LDDL_HIP(hipGetLastError());
-  return 0;
+  return denoise_launch(
+      ContBits{c ? c->d_cont_bits : nullptr, c ? c->vocab_size : 0}, c ? nullptr : "null ctx",
+      c && c->d_cont_bits ? nullptr : "the context has no continuation bitmap", stream, d_ids,
+      d_sent_off, d_sent_len, d_doc_sent_off, d_rows, batch, seq_len, d_input_ids,
+      d_attention_mask, d_decoder_input_ids, d_labels, d_src_lengths, bos_id, eos_id, pad_id,
+      mask_id, decoder_start_id, ignore_index, vocab_len, seed, counter, draw_stride, permute_p,
+      random_ratio, params);
+}
+
+extern "C" int lddl_bart_denoise_bits(const uint32_t* d_cont_bits, int64_t n_ids, void* stream,
+                                      const int32_t* d_ids, const int64_t* d_sent_off,
+                                      const int32_t* d_sent_len, const int64_t* d_doc_sent_off,
+                                      const int64_t* d_rows, int32_t batch, int32_t seq_len,
+                                      int64_t* d_input_ids, int64_t* d_attention_mask,
+                                      int64_t* d_decoder_input_ids, int64_t* d_labels,
+                                      int32_t* d_src_lengths, int64_t bos_id, int64_t eos_id,
+                                      int64_t pad_id, int64_t mask_id, int64_t decoder_start_id,
+                                      int64_t ignore_index, int64_t vocab_len, uint64_t seed,
+                                      uint64_t counter, int32_t draw_stride, float permute_p,
+                                      float random_ratio, const lddl_denoise_params* params) {
+  const bool ok = d_cont_bits && n_ids >= 1 && n_ids <= INT32_MAX;
+  return denoise_launch(
+      ContBits{d_cont_bits, (int32_t)(ok ? n_ids : 0)},
+      ok ? nullptr : "null continuation bitmap, or n_ids outside [1, 2^31)", nullptr, stream,
+      d_ids, d_sent_off, d_sent_len, d_doc_sent_off, d_rows, batch, seq_len, d_input_ids,
+      d_attention_mask, d_decoder_input_ids, d_labels, d_src_lengths, bos_id, eos_id, pad_id,
+      mask_id, decoder_start_id, ignore_index, vocab_len, seed, counter, draw_stride, permute_p,
+      random_ratio, params);
 }

@@ -105,8 +105,9 @@ def bart_denoise(ctx, ids, sent_off, sent_len, doc_sent_off, rows=None, seq_len=
     A sample keeps its first L - 2 pieces. seq_len=None makes L the longest sample + 2, rounded
     up to sequence_length_alignment, which costs the one device sync; check=True refuses a row
     index outside the batch (IndexError; the same sync). The special ids default to the
-    context's [CLS], [SEP], [PAD] and [MASK], decoder_start_id to eos_id, vocab_len to
-    len(ctx). params: a DenoiseParams made by hand in place of the one of mask_ratio and the
+    context's [CLS], [SEP], [PAD] and [MASK] (a `BpeContext` in place of the `Context`: <s>,
+    </s>, <pad> and <mask>, and a word begins at a piece that opens with a space),
+    decoder_start_id to eos_id, vocab_len to len(ctx). params: a DenoiseParams made by hand in place of the one of mask_ratio and the
     weights (e.g. p_start = 1 and cum all 1: an inserted token before every word)."""
     ratio, seed, counter, weights = check_noise(mask, poisson_lambda, span_weights,
                                                 permute_sentence_ratio, random_ratio,
@@ -116,13 +117,16 @@ def bart_denoise(ctx, ids, sent_off, sent_len, doc_sent_off, rows=None, seq_len=
     from .._native import check as _check, lib
     from ..context import _ptr, _stream
     sp = ctx.special_ids
-    bos = sp['[CLS]'] if bos_id is None else int(bos_id)
-    eos = sp['[SEP]'] if eos_id is None else int(eos_id)
-    pad = sp['[PAD]'] if pad_id is None else int(pad_id)
-    msk = sp['[MASK]'] if mask_id is None else int(mask_id)
+    from ..bpe import BpeContext
+    # a BpeContext: its bitmap goes to the _bits entry
+    bits = ctx.cont_bits if isinstance(ctx, BpeContext) else None
+    names = ('[CLS]', '[SEP]', '[PAD]', '[MASK]') if bits is None else \
+        ('<s>', '</s>', '<pad>', '<mask>')
+    bos, eos, pad, msk = (sp[n] if v is None else int(v)
+                          for n, v in zip(names, (bos_id, eos_id, pad_id, mask_id)))
     if min(bos, eos, pad, msk) < 0:
-        raise ValueError('the vocab lacks [CLS], [SEP], [PAD] or [MASK]: pass bos_id, eos_id, '
-                         'pad_id and mask_id')
+        raise ValueError('the vocab lacks {}, {}, {} or {}: pass bos_id, eos_id, pad_id and '
+                         'mask_id'.format(*names))
     dec = eos if decoder_start_id is None else int(decoder_start_id)
     if params is None:
         params = make_params(ratio, weights)
@@ -148,8 +152,10 @@ def bart_denoise(ctx, ids, sent_off, sent_len, doc_sent_off, rows=None, seq_len=
     dev = ctx.device
     out = {k: torch.empty(B, L, dtype=torch.long, device=dev) for k in OUTPUTS}
     out['src_lengths'] = torch.empty(B, dtype=torch.int32, device=dev)
-    _check(lib.lddl_bart_denoise(
-        ctx.handle, _stream(), _ptr(ids), _ptr(sent_off), _ptr(sent_len), _ptr(doc_sent_off),
+    entry, owner = (lib.lddl_bart_denoise, (ctx.handle,)) if bits is None else \
+        (lib.lddl_bart_denoise_bits, bits)
+    _check(entry(
+        *owner, _stream(), _ptr(ids), _ptr(sent_off), _ptr(sent_len), _ptr(doc_sent_off),
         _ptr(rows), B, L, *[_ptr(out[k]) for k in OUTPUTS], _ptr(out['src_lengths']), bos, eos,
         pad, msk, dec, int(ignore_index), len(ctx) if vocab_len is None else int(vocab_len), seed,
         counter, L if draw_stride is None else int(draw_stride), float(permute_sentence_ratio),
@@ -172,11 +178,22 @@ def shard_files(path):
 
 
 def validate_args(path=None, vocab_file=None, batch_size=None, max_seq_length=512,
-                  mask_ratio=0.3, rank=None, world=None, round_bytes=32 << 20, **kw):
+                  mask_ratio=0.3, rank=None, world=None, round_bytes=32 << 20, bpe=None,
+                  bpe_tables=None, **kw):
     """Every argument error of get_bart_pretrain_data_loader, raised before the GPU is touched.
-    Returns (files, format)."""
+    Returns (files, format). bpe_tables: a list that takes the parsed (tokens, vocab, merges)
+    of bpe=, so that the loader does not read the two files again."""
     shards = shard_files(path)
-    if not isinstance(vocab_file, str) or not os.path.isfile(vocab_file):
+    if bpe is not None:
+        if not isinstance(bpe, (tuple, list)) or len(bpe) != 2:
+            raise ValueError('bpe must be (vocab_json, merges_txt), not {!r}'.format(bpe))
+        if vocab_file is not None:
+            raise ValueError('pass vocab_file (WordPiece) or bpe=, not both')
+        from ..bpe import load_tables
+        tables = load_tables(*bpe)
+        if bpe_tables is not None:
+            bpe_tables[:] = tables
+    elif not isinstance(vocab_file, str) or not os.path.isfile(vocab_file):
         raise FileNotFoundError('vocab_file {!r}: a local vocab.txt is required'.format(vocab_file))
     if not isinstance(batch_size, int) or isinstance(batch_size, bool) or batch_size < 1:
         raise ValueError('batch_size must be a positive int')
@@ -209,7 +226,8 @@ class BartPretrainLoader:
     """The iterable get_bart_pretrain_data_loader returns; each iter() is one epoch."""
 
     def __init__(self, **kw):
-        self.files, self.format = validate_args(**kw)
+        self._bpe_tables = []
+        self.files, self.format = validate_args(bpe_tables=self._bpe_tables, **kw)
         self._kw = kw
         self._epoch = kw['start_epoch']
         self._ctx = None
@@ -223,7 +241,17 @@ class BartPretrainLoader:
         kw = self._kw
         self.rank, self.world = (get_rank(), get_world_size()) if kw['rank'] is None else \
             (kw['rank'], kw['world'])
-        self._ctx = Context(kw['vocab_file'], do_lower_case=kw['do_lower_case'])
+        # Punkt's tables live in a Context. With bpe= it is one of the packaged WordPiece
+        # vocabulary that only segments: its 30 k-entry tokenizer tables are built and never
+        # read, the price of not giving Punkt an owner of its own here.
+        self._bpe = None
+        if kw['bpe'] is not None:
+            from ..bpe import BpeContext
+            from ..context import ASSETS
+            self._bpe = BpeContext.from_tables(self._bpe_tables[0], self._bpe_tables[2],
+                                               vocab=self._bpe_tables[1])
+        self._ctx = Context(kw['vocab_file'] if self._bpe is None else os.path.join(
+            ASSETS, 'vocab_synth_uncased_30522.txt'), do_lower_case=kw['do_lower_case'])
         pp = kw['punkt_params']
         if pp is None or isinstance(pp, str):
             pp = punkt_params(SimpleNamespace(punkt_params=pp))
@@ -257,7 +285,10 @@ class BartPretrainLoader:
         doc_off = np.zeros(len(chunks) + 1, np.int64)
         np.cumsum([len(c) for c in chunks], out=doc_off[1:])
         sent_off, doc_sent_off = punkt.segment(ctx, text, torch.from_numpy(doc_off).to(ctx.device))
-        ids, sent_len = ctx.tokenize(text, sent_off, self._kw['max_pieces'])
+        if self._bpe is None:
+            ids, sent_len = ctx.tokenize(text, sent_off, self._kw['max_pieces'])
+        else:  # per document: a pre-token goes to the sentence of its last byte
+            ids, sent_len = self._bpe.tokenize(text, sent_off, doc_sent_off, self._kw['max_pieces'])
         table = (ids, sent_off, sent_len, doc_sent_off)
         return table, sample_lengths(sent_len, doc_sent_off).cpu().numpy()
 
@@ -269,7 +300,7 @@ class BartPretrainLoader:
     def denoise(self, table, rows, L, epoch, step):
         kw = self._kw
         return bart_denoise(
-            self._ctx, *table, rows=rows, seq_len=L, mask=(kw['mask_ratio'], self.seed,
+            self._bpe or self._ctx, *table, rows=rows, seq_len=L, mask=(kw['mask_ratio'], self.seed,
                                                            (epoch << 32) | step),
             permute_sentence_ratio=kw['permute_sentence_ratio'], random_ratio=kw['random_ratio'],
             ignore_index=kw['ignore_index'], check=False, params=self._params,
@@ -306,7 +337,8 @@ def get_bart_pretrain_data_loader(path, vocab_file=None, batch_size=None, max_se
                                   sequence_length_alignment=8, ignore_index=-100,
                                   base_seed=12345, start_epoch=0, rank=None, world=None,
                                   drop_last=False, round_bytes=32 << 20, max_pieces=512,
-                                  do_lower_case=True, punkt_params=None, special_ids=None):
+                                  do_lower_case=True, punkt_params=None, special_ids=None,
+                                  bpe=None):
     """BART pretraining batches from the shards of `preprocess_bart_pretrain` (parquet or txt)
     under `path` (past the reference, which has no BART loader). One process, one
     stream, no DataLoader workers: a round of shards (at most round_bytes; this rank's are
@@ -316,5 +348,8 @@ def get_bart_pretrain_data_loader(path, vocab_file=None, batch_size=None, max_se
     bart_denoise's dicts with L = the batch's longest chunk + 2, aligned, at most
     max_seq_length (a longer chunk keeps its first max_seq_length - 2 pieces). special_ids:
     bos_id, eos_id, pad_id, mask_id, decoder_start_id and vocab_len as bart_denoise takes them.
+    bpe=(vocab_json, merges_txt) in place of vocab_file: the chunks are tokenized by the
+    byte-level BPE of a GPT-2 / RoBERTa / BART checkpoint (`lddl_amd.bpe.BpeContext`, DESIGN
+    §29), per chunk, and bos / eos / pad / mask are the vocabulary's <s>, </s>, <pad>, <mask>.
     The ranks do not agree on a number of steps: each yields what its shards hold."""
     return BartPretrainLoader(**dict(locals()))
