@@ -971,6 +971,88 @@ int lddl_bpe_pretoken_stats(lddl_bpe* bpe, void* stream, const uint8_t* d_text, 
                             const int64_t* d_sent_off, int64_t n_sent,
                             const int64_t* d_doc_sent_off, int64_t n_doc, int64_t* d_stats);
 
+/* ---------------------------------------------------------------------------------------------
+ * RoBERTa blocks (past the reference): rows of contiguous whole sentences without
+ * NSP, cut over a whole round of sentences and collated with dynamic masking. FULL-SENTENCES
+ * and DOC-SENTENCES of the RoBERTa paper; fairseq's TokenBlockDataset(break_mode='complete' /
+ * 'complete_doc') with MaskTokensDataset. The input is a token table as lddl_tokenize and
+ * lddl_bpe_tokenize lay it out: d_ids, d_sent_off[n_sent + 1], d_sent_len[n_sent] (its flag
+ * bits above bit 29 are masked off: len(s) = d_sent_len[s] & (2^30 - 1)) and
+ * d_doc_sent_off[n_doc + 1]. T = seq_len - 2 >= 1.
+ *   cost    sep(s) = 1 in LDDL_BLOCKS_FULL if s is the last sentence of non-zero length of its
+ *     document, else 0; always 0 in LDDL_BLOCKS_DOC. c(s) = min(len(s) + sep(s), T); the
+ *     sentence keeps its first c(s) - sep(s) pieces; an empty sentence costs 0. The separator
+ *     belongs to the end of its document, so a sentence's cost does not depend on where its
+ *     block starts. This is the one deviation from fairseq, where the blank line between two
+ *     documents is an item of its own and may open a block.
+ *   jump    P = the exclusive prefix sum of c in int64 (P[n_sent] the total); next(i) = the
+ *     largest j > i with P[j] - P[i] <= T (next(i) >= i + 1 because c <= T); in LDDL_BLOCKS_DOC
+ *     next(i) is at most the end of i's document, the first entry of d_doc_sent_off above i.
+ *   blocks  b_0 = 0, b_{k + 1} = next(b_k) until n_sent is reached; block k is the sentences
+ *     [b_k, b_{k + 1}) and its length P[b_{k + 1}] - P[b_k]. A block of length 0 is not emitted
+ *     (a document of empty sentences only in DOC mode; an input of empty sentences only).
+ *
+ * lddl_blocks_plan writes d_piece_off[n_sent + 1] = P, d_sent_sep[n_sent] = sep, the emitted
+ * blocks in order as d_block_sent[k] = b_k and d_block_len[k], d_block_sent[n_blocks] = n_sent
+ * and d_n_blocks[0]; d_block_sent and d_block_len have room for n_sent + 1 entries. Block k ends
+ * at d_block_sent[k + 1] wherever the next emitted block starts: the sentences between are
+ * empty. Asynchronous on `stream`, no host wait (the caller reads d_n_blocks once per round);
+ * the temporaries, 17 bytes a sentence, come from an arena that the library keeps per device
+ * and lddl_blocks_release() empties (it waits for the work that used them). Fails with -1
+ * before anything is launched on seq_len < 3 or > 2^24, a mode that is neither, a negative
+ * size, a NULL output, or, with n_sent > 0, a NULL input. n_sent = 0 gives n_blocks = 0.
+ * The walk is on two levels, tiles of LDDL_BLOCKS_TILE sentences (csrc/blocks_plan.hip).
+ *
+ * lddl_collate_blocks / lddl_collate_blocks_masked: output row i is block d_rows[i] (d_rows
+ * NULL: block i; the indices are the caller's to check) of the plan made with the same seq_len:
+ *   input_ids = bos_id, the kept pieces of the block's sentences in order with eos_id behind a
+ *     sentence that has sep = 1, eos_id, then pad_id; attention_mask = 1 up to and including
+ *     the closing eos_id.
+ *   specials   bos, every eos (separators included) and pad are special: never masked, no
+ *     word, and a span runs on over them as in the n-gram entry points above.
+ *   masking    slot x of row i draws r = the Philox call of lddl_mask_dynamic at flat index
+ *     i * seq_len + x under seed and counter. params NULL: per token, masked iff not special
+ *     and u01(r.x) < mlm_probability. params given (word mode): a slot is a head iff it is not
+ *     special and it is the first kept piece of a sentence or its id is no continuation id
+ *     (bit id of d_cont_bits[id >> 5]; ids outside [0, n_ids) never continue a word:
+ *     lddl_bpe_cont_bits, or a WordPiece "##" bitmap); words, starts (params->p_start), lengths
+ *     and the prefix maximum are those of the n-gram entry points, mlm_probability is unread,
+ *     and n = 1 is whole-word masking. Both modes: 80 / 10 / 10 with mask_id and the random id
+ *     (r.w * vocab_len) >> 32, labels = the id where masked, else ignore_index.
+ *   unmasked   d_special_tokens_mask (1 on special slots) is written in place of labels.
+ * All outputs are int64 [batch, seq_len], every element written exactly once. One launch,
+ * asynchronous, no temporaries. A block of more than LDDL_BLOCKS_LDS_SENTS sentences is served
+ * from global memory past that many. Both fail with -1 before anything is launched on
+ * seq_len < 3 or > 2^24 and, with batch > 0, a NULL table, plan or output; the masked one also
+ * on params that lddl_span_params_make cannot have written, mlm_probability outside [0, 1],
+ * vocab_len outside [1, 2^32], n_ids outside [1, 2^31), and params with a NULL bitmap.
+ * batch <= 0 returns 0 and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define LDDL_BLOCKS_FULL 0
+#define LDDL_BLOCKS_DOC 1
+#define LDDL_BLOCKS_TILE 2048
+#define LDDL_BLOCKS_LDS_SENTS 256
+int lddl_blocks_plan(void* stream, const int32_t* d_sent_len, int64_t n_sent,
+                     const int64_t* d_doc_sent_off, int64_t n_doc, int32_t seq_len, int32_t mode,
+                     int64_t* d_piece_off, uint8_t* d_sent_sep, int64_t* d_block_sent,
+                     int32_t* d_block_len, int64_t* d_n_blocks);
+int lddl_blocks_release(void);
+int lddl_collate_blocks(void* stream, const int32_t* d_ids, const int64_t* d_sent_off,
+                        const int64_t* d_piece_off, const uint8_t* d_sent_sep,
+                        const int64_t* d_block_sent, const int64_t* d_rows, int32_t batch,
+                        int32_t seq_len, int64_t* d_input_ids, int64_t* d_attention_mask,
+                        int64_t* d_special_tokens_mask, int64_t bos_id, int64_t eos_id,
+                        int64_t pad_id);
+int lddl_collate_blocks_masked(const uint32_t* d_cont_bits, int64_t n_ids, void* stream,
+                               const int32_t* d_ids, const int64_t* d_sent_off,
+                               const int64_t* d_piece_off, const uint8_t* d_sent_sep,
+                               const int64_t* d_block_sent, const int64_t* d_rows, int32_t batch,
+                               int32_t seq_len, int64_t* d_input_ids, int64_t* d_attention_mask,
+                               int64_t* d_labels, int64_t bos_id, int64_t eos_id, int64_t pad_id,
+                               int64_t mask_id, float mlm_probability, int64_t ignore_index,
+                               int64_t vocab_len, uint64_t seed, uint64_t counter,
+                               const lddl_span_params* params);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,16 @@ SIGNATURES = {
                                          c_vp, c_vp]),
     'lddl_bpe_pretoken_stats': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                                c_vp]),
+    # RoBERTa blocks (lddl_amd/torch/roberta.py); a nullable const lddl_span_params* comes last
+    'lddl_blocks_plan': (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp]),
+    'lddl_blocks_release': (ctypes.c_int, []),
+    'lddl_collate_blocks': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                           c_vp, c_vp, c_vp, c_i64, c_i64, c_i64]),
+    'lddl_collate_blocks_masked': (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                  c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64,
+                                                  c_i64, c_i64, c_i64, ctypes.c_float, c_i64,
+                                                  c_i64, c_u64, c_u64, c_vp]),
 }
 
 

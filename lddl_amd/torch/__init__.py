@@ -5,7 +5,9 @@ the reference) and the online loaders (`get_bert_pretrain_online_data_loader`, `
 raw text to batches without shards; `get_bert_pretrain_online_packed_data_loader`: the same with
 sequence packing planned and collated on the device; both past the reference) and the compact
 MLM targets (`compact_labels`, `CompactMLMTargets`: a `collate_fn` for every loader) and BART
-denoising (`bart_denoise`, `get_bart_pretrain_data_loader`; past the reference) are resolved
+denoising (`bart_denoise`, `get_bart_pretrain_data_loader`; past the reference) and the RoBERTa
+loader (`roberta_blocks`, `collate_blocks`, `get_roberta_pretrain_data_loader`: FULL- and
+DOC-SENTENCES blocks cut and collated on the device; past the reference) are resolved
 lazily, so that DataLoader workers started with `spawn` / `forkserver` import only the
 worker-side modules (`packing`, `seqpack`, `datasets`), never the native library."""
 
@@ -25,4 +27,7 @@ def __getattr__(name):
     if name in ('bart_denoise', 'get_bart_pretrain_data_loader'):
         from . import denoise
         return getattr(denoise, name)
+    if name in ('roberta_blocks', 'collate_blocks', 'get_roberta_pretrain_data_loader'):
+        from . import roberta
+        return getattr(roberta, name)
     raise AttributeError(name)
