@@ -1053,6 +1053,61 @@ int lddl_collate_blocks_masked(const uint32_t* d_cont_bits, int64_t n_ids, void*
                                int64_t vocab_len, uint64_t seed, uint64_t counter,
                                const lddl_span_params* params);
 
+/* ---------------------------------------------------------------------------------------------
+ * T5 span corruption (past the reference): an exact number of noise tokens in an
+ * exact number of spans per row, written as two compacted rows with matching sentinel ids. T5's
+ * random_spans_noise_mask with noise_span_to_unique_sentinel; the two stated deviations are the
+ * fixed-point counts and the RNG. Row i is block d_rows[i] (NULL: block i; the indices are the
+ * caller's to check) of a lddl_blocks_plan plan made with plan_seq_len, FULL or DOC. Its tokens
+ * t[0 .. n) are the block's kept pieces in order with eos_id where the plan put a separator
+ * (an ordinary token here); n = P[b_{k + 1}] - P[b_k] <= T = plan_seq_len - 2. No bos.
+ *   counts  in int64, no floating point: dq = round(noise_density * 65536) and iq = round(65536
+ *     / mean_noise_span_length) are the caller's, made once.
+ *     N = clamp((n * dq + 32768) >> 16, 1, n - 1) noise tokens,
+ *     k = clamp((N * iq + 32768) >> 16, 1, min(N, n - N, n_sentinels)) spans, M = n - N;
+ *     n < 2: N = k = 0 (the row is its tokens and eos, the target eos alone).
+ *   keys    for u in [0, max(N, M) - 1), r(u) = the Philox call of lddl_mask_dynamic at flat
+ *     index i * plan_seq_len + u under seed and counter; noise item u + 1 has the key r.x >> 8,
+ *     non-noise item u + 1 the key r.y >> 8 (24 bits).
+ *   segments  of the noise items 1 .. N - 1 the k - 1 with the smallest (key, item) pairs in
+ *     lexicographic order open a segment, and so does item 0; B[g] = the first item of noise
+ *     segment g in ascending order, B[k] = N. The non-noise items 1 .. M - 1 give A[g] in the
+ *     same way from their keys, A[k] = M. Every segment holds an item.
+ *   order   non-noise segment 0, noise segment 0, non-noise segment 1, ...: the row starts clean
+ *     and ends in noise. Noise item j of segment g is t[j + A[g + 1]], non-noise item m of
+ *     segment h is t[m + B[h]]. Sentinel g has the id sentinel_first - g.
+ *   input_ids [batch, in_len]: for g = 0 .. k - 1 non-noise segment g, then sentinel g; then
+ *     eos_id; then pad_id. attention_mask = 1 up to and including that eos_id.
+ *   labels [batch, tgt_len]: for g = 0 .. k - 1 sentinel g, then noise segment g; then eos_id;
+ *     then ignore_index (no closing sentinel).
+ *   decoder_input_ids [batch, tgt_len]: decoder_start_id, then labels shifted right by one with
+ *     pad_id in the slots where labels is ignore_index's fill.
+ *   src_lengths, tgt_lengths int64 [batch] = M + k + 1 and N + k + 1, never truncated.
+ * An id whose slot lies at or past the last slot of a row that is too narrow is dropped, and the
+ * eos_id sits in the last slot. Every output element is written exactly once. One launch,
+ * asynchronous on `stream`, no temporaries, no atomics on global memory.
+ *
+ * lddl_t5_lengths (host only): *in_len = M + k + 1 and *tgt_len = N + k + 1 at n = tokens. Both
+ * are non-decreasing in n, so no row of a plan with T = tokens overflows them.
+ * Both fail with -1 before anything is launched on plan_seq_len < 3 or > 2^24 (tokens < 1 or
+ * > 2^24 - 2), in_len or tgt_len outside [1, 2^24], dq outside [1, 65535], iq outside
+ * [1, 65536], n_sentinels outside [1, LDDL_T5_MAX_SPANS], sentinel_first - n_sentinels + 1 < 0
+ * and, lddl_t5_lengths always and lddl_t5_corrupt with batch > 0, a NULL table, plan or output.
+ * batch <= 0 returns 0 and launches nothing.
+ * ------------------------------------------------------------------------------------------- */
+#define LDDL_T5_MAX_SPANS 256
+int lddl_t5_lengths(int64_t tokens, int32_t dq, int32_t iq, int32_t n_sentinels, int64_t* in_len,
+                    int64_t* tgt_len);
+int lddl_t5_corrupt(void* stream, const int32_t* d_ids, const int64_t* d_sent_off,
+                    const int64_t* d_piece_off, const uint8_t* d_sent_sep,
+                    const int64_t* d_block_sent, const int64_t* d_rows, int32_t batch,
+                    int32_t plan_seq_len, int32_t in_len, int32_t tgt_len, int32_t dq, int32_t iq,
+                    int32_t n_sentinels, int64_t sentinel_first, int64_t eos_id, int64_t pad_id,
+                    int64_t decoder_start_id, int64_t ignore_index, uint64_t seed,
+                    uint64_t counter, int64_t* d_input_ids, int64_t* d_attention_mask,
+                    int64_t* d_labels, int64_t* d_decoder_input_ids, int64_t* d_src_lengths,
+                    int64_t* d_tgt_lengths);
+
 #ifdef __cplusplus
 }
 #endif

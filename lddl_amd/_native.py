@@ -186,6 +186,12 @@ SIGNATURES = {
                                                   c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64,
                                                   c_i64, c_i64, c_i64, ctypes.c_float, c_i64,
                                                   c_i64, c_u64, c_u64, c_vp]),
+    # T5 span corruption (lddl_amd/torch/t5.py)
+    'lddl_t5_lengths': (ctypes.c_int, [c_i64, c_i32, c_i32, c_i32, c_i64p, c_i64p]),
+    'lddl_t5_corrupt': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                       c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64,
+                                       c_i64, c_i64, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp]),
 }
 
 

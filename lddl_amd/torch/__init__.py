@@ -7,8 +7,9 @@ sequence packing planned and collated on the device; both past the reference) an
 MLM targets (`compact_labels`, `CompactMLMTargets`: a `collate_fn` for every loader) and BART
 denoising (`bart_denoise`, `get_bart_pretrain_data_loader`; past the reference) and the RoBERTa
 loader (`roberta_blocks`, `collate_blocks`, `get_roberta_pretrain_data_loader`: FULL- and
-DOC-SENTENCES blocks cut and collated on the device; past the reference) are resolved
-lazily, so that DataLoader workers started with `spawn` / `forkserver` import only the
+DOC-SENTENCES blocks cut and collated on the device; past the reference) and T5 span corruption
+(`t5_corrupt`, `t5_lengths`, `t5_tokens_length`, `get_t5_pretrain_data_loader`: exact-count
+spans and sentinel rows from the same blocks; past the reference) are resolved lazily, so that DataLoader workers started with `spawn` / `forkserver` import only the
 worker-side modules (`packing`, `seqpack`, `datasets`), never the native library."""
 
 
@@ -30,4 +31,7 @@ def __getattr__(name):
     if name in ('roberta_blocks', 'collate_blocks', 'get_roberta_pretrain_data_loader'):
         from . import roberta
         return getattr(roberta, name)
+    if name in ('t5_lengths', 't5_tokens_length', 't5_corrupt', 'get_t5_pretrain_data_loader'):
+        from . import t5
+        return getattr(t5, name)
     raise AttributeError(name)

@@ -242,8 +242,13 @@ class RobertaPretrainLoader:
         sent_off, doc_sent_off = punkt.segment(self._ctx, text, torch.from_numpy(doc_off).to(dev))
         ids, sent_len = self.bpe.tokenize(text, sent_off, doc_sent_off, self._kw['max_pieces'])
         table = (ids, sent_off, sent_len, doc_sent_off)
-        plan, n = roberta_blocks(table, self._kw['max_seq_length'], self._kw['mode'])
+        plan, n = roberta_blocks(table, self.plan_seq_len(), self._kw['mode'])
         return table, plan, n
+
+    def plan_seq_len(self):
+        """The seq_len the round's blocks are cut for; with `collate`, what a subclass replaces
+        (the T5 loader of t5.py)."""
+        return self._kw['max_seq_length']
 
     def order(self, epoch, rnd, n):
         """The seeded shuffle of a round's n blocks."""
