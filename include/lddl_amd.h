@@ -972,6 +972,84 @@ int lddl_bpe_pretoken_stats(lddl_bpe* bpe, void* stream, const uint8_t* d_text, 
                             const int64_t* d_doc_sent_off, int64_t n_doc, int64_t* d_stats);
 
 /* ---------------------------------------------------------------------------------------------
+ * SentencePiece unigram (T5 / mT5 / ALBERT / XLNet / XLM-R / mBART vocabularies; past the
+ * reference). Input and output are lddl_bpe_tokenize's: d_text[n_bytes],
+ * d_sent_off[n_sent + 1] rising from 0 to n_bytes, d_doc_sent_off accepted and unread (a document
+ * starts where a sentence does, and a word never crosses a sentence start); sentence s has its
+ * pieces at d_ids[d_sent_off[s] ..] and d_sent_len[s] = min(pieces, max_pieces, bytes of s): the
+ * first ones are kept and no flag bit is set. The bytes bound it because the slots do ("a b c"
+ * on a vocabulary without "▁a" has six pieces in five bytes).
+ *
+ * Words. A space is the byte 0x20; with LDDL_UNIGRAM_ASCII_WS in `flags` the bytes 0x09, 0x0A,
+ * 0x0C and 0x0D are spaces too. A word is a maximal run of non-space bytes inside one sentence,
+ * and it is encoded alone as the bytes E2 96 81 (U+2581, the space mark) followed by its own:
+ * SentencePiece with add_dummy_prefix, remove_extra_whitespaces, escape_whitespaces and
+ * split_by_whitespace at their defaults. That is exact because lddl_unigram_create refuses a
+ * vocabulary with the mark at a non-leading position of a piece, so that the lattice of a
+ * sentence falls apart at every word. A sentence without a word has no pieces.
+ * Characters. A lead byte C2-DF, E0-EF, F0-F4 with its 1, 2, 3 continuation bytes (80-BF) inside
+ * the word is one character; every other byte (a stray continuation byte, the lead of a
+ * truncated sequence, C0, C1, F5-FF) is a character of length 1.
+ * Viterbi per word of n bytes, mark included: best[0] = 0.0f. For each character start s in
+ * rising order and every NORMAL or USER_DEFINED piece that equals bytes[s:e], cand = best[s] +
+ * score as one float32 add; cand replaces best[e] iff best[e] is unset or cand > best[e] (strict:
+ * the earlier start wins a tie). If no piece of exactly one character matched at s, that
+ * character is a candidate too, with id unk_id and score unk_score = (the lowest NORMAL score) -
+ * 10.0f. The path is read back from best[n]; consecutive unk_id pieces fuse into one. There is
+ * no other floating point. The score of a USER_DEFINED piece is read as given (lddl_amd.unigram
+ * passes SentencePiece's length * max score - 0.1 for them).
+ * Deviations. The model's normaliser (nmt_nfkc and so on) is not applied beyond the space
+ * classes: text it would change is tokenized as it stands. Byte fallback is not built; CONTROL,
+ * UNKNOWN, UNUSED and BYTE pieces never match text. A word of more than LDDL_UNIGRAM_MAX_WORD
+ * bytes is encoded in consecutive slices of at most that many of its bytes, each cut at the
+ * last character start that fits, each with a Viterbi and an unknown fusion of its own; only
+ * the first slice carries the mark.
+ *
+ * lddl_unigram_create: piece i is piece_bytes[piece_off[i] .. piece_off[i + 1]) with scores[i]
+ * and types[i] (1 NORMAL, 2 UNKNOWN, 3 CONTROL, 4 USER_DEFINED, 5 UNUSED, 6 BYTE, as in
+ * sentencepiece_model.proto); flags = 0 or LDDL_UNIGRAM_ASCII_WS. Fails with -1
+ * (lddl_last_error) on a NULL array, n_pieces outside [1, 2^20], no NORMAL or USER_DEFINED
+ * piece that is the mark alone, the mark at an interior position of such a piece, unk_id out of
+ * range or not the one UNKNOWN piece, an empty or repeated such piece, a score that is not
+ * finite or beyond 1e30 in magnitude (the sums of a slice stay finite), and more than
+ * LDDL_UNIGRAM_MAX_NEST pieces on one root-to-leaf path of the byte trie: that is the most
+ * matches one start can have, and max_sentencepiece_length = 16, the default, keeps a model
+ * inside it. Builds on `device`: the trie as an open-addressing table (node, byte) -> (child,
+ * piece or -1, score) of 16-byte slots, at most half full, a 256-entry table for the root, and
+ * the bitmap of lddl_unigram_cont_bits: bit id set iff piece id is NORMAL or USER_DEFINED and
+ * does not start with the mark (the shape of lddl_bpe_cont_bits; an unknown piece counts as a
+ * word's beginning). Its pointers live as long as the lddl_unigram.
+ * lddl_unigram_info: the pieces, the trie's nodes, the bytes of the two tables, unk_score; any
+ * pointer may be NULL.
+ * lddl_unigram_tokenize: asynchronous on `stream`, no host wait; its temporaries (about 5 bytes
+ * per byte of text) come from an arena the lddl_unigram owns and are reused by the next call.
+ * Fails with -1 on a NULL lddl_unigram, a negative size, max_pieces < 1, or, with n_sent > 0, a
+ * NULL array; n_sent = 0 launches nothing.
+ * lddl_unigram_word_stats: measurement aid, the word marks alone on the same input. d_stats
+ * (device int64[3]) = the words, those of at most 64 bytes that cross the end of the 64-byte
+ * tile they start in (the tile pass's second window) and those longer than 64 bytes (the long
+ * pass of csrc/unigram_viterbi.hip).
+ * ------------------------------------------------------------------------------------------- */
+#define LDDL_UNIGRAM_MAX_WORD 1024
+#define LDDL_UNIGRAM_MAX_NEST 16
+#define LDDL_UNIGRAM_ASCII_WS 1
+typedef struct lddl_unigram lddl_unigram;
+int lddl_unigram_create(int device, const uint8_t* piece_bytes, const int64_t* piece_off,
+                        const float* scores, const int32_t* types, int64_t n_pieces,
+                        int32_t unk_id, int32_t flags, lddl_unigram** out);
+int lddl_unigram_destroy(lddl_unigram* unigram);
+int lddl_unigram_info(const lddl_unigram* unigram, int64_t* n_pieces, int64_t* n_nodes,
+                      int64_t* table_bytes, float* unk_score, int32_t* max_word);
+int lddl_unigram_cont_bits(const lddl_unigram* unigram, const uint32_t** d_bits, int64_t* n_ids);
+int lddl_unigram_tokenize(lddl_unigram* unigram, void* stream, const uint8_t* d_text,
+                          int64_t n_bytes, const int64_t* d_sent_off, int64_t n_sent,
+                          const int64_t* d_doc_sent_off, int64_t n_doc, int32_t max_pieces,
+                          int32_t* d_ids, int32_t* d_sent_len);
+int lddl_unigram_word_stats(lddl_unigram* unigram, void* stream, const uint8_t* d_text,
+                            int64_t n_bytes, const int64_t* d_sent_off, int64_t n_sent,
+                            const int64_t* d_doc_sent_off, int64_t n_doc, int64_t* d_stats);
+
+/* ---------------------------------------------------------------------------------------------
  * RoBERTa blocks (past the reference): rows of contiguous whole sentences without
  * NSP, cut over a whole round of sentences and collated with dynamic masking. FULL-SENTENCES
  * and DOC-SENTENCES of the RoBERTa paper; fairseq's TokenBlockDataset(break_mode='complete' /

@@ -176,6 +176,16 @@ SIGNATURES = {
                                          c_vp, c_vp]),
     'lddl_bpe_pretoken_stats': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                                c_vp]),
+    # SentencePiece unigram (lddl_amd/unigram.py)
+    'lddl_unigram_create': (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32,
+                                           ctypes.POINTER(c_vp)]),
+    'lddl_unigram_destroy': (ctypes.c_int, [c_vp]),
+    'lddl_unigram_info': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'lddl_unigram_cont_bits': (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
+    'lddl_unigram_tokenize': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                             c_i32, c_vp, c_vp]),
+    'lddl_unigram_word_stats': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                               c_vp]),
     # RoBERTa blocks (lddl_amd/torch/roberta.py); a nullable const lddl_span_params* comes last
     'lddl_blocks_plan': (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp,
                                         c_vp, c_vp, c_vp]),

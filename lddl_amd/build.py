@@ -51,7 +51,9 @@ BUILD_ID_H = os.path.join(CSRC, 'build_id.h')
 _NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 UNIT_FLAGS = {u: _NO_PACKED_FP32 for u in ('denoise.hip', 'bpe_split.hip', 'bpe_merge.hip',
                                            'bpe_api.hip', 'blocks_plan.hip',
-                                           'blocks_collate.hip', 't5_corrupt.hip')}
+                                           'blocks_collate.hip', 't5_corrupt.hip',
+                                           'unigram_match.hip', 'unigram_viterbi.hip',
+                                           'unigram_api.hip')}
 UNIT_FLAGS_ID = repr(sorted(UNIT_FLAGS.items()))
 
 

@@ -110,8 +110,9 @@ def collate_blocks(bpe_or_ctx, table, plan, rows=None, seq_len=None, mask=None, 
     from .._native import check, lib
     from ..bpe import BpeContext
     from ..context import _ptr, _stream
+    from ..unigram import UnigramContext
     ctx, sp = bpe_or_ctx, dict(special_ids or {})
-    names = ('<s>', '</s>', '<pad>', '<mask>') if isinstance(ctx, BpeContext) else \
+    names = ('<s>', '</s>', '<pad>', '<mask>') if isinstance(ctx, (BpeContext, UnigramContext)) else \
         ('[CLS]', '[SEP]', '[PAD]', '[MASK]')
     bos, eos, pad, msk = (int(sp[k]) if k in sp else ctx.special_ids.get(n, -1)
                           for k, n in zip(('bos_id', 'eos_id', 'pad_id', 'mask_id'), names))
@@ -156,16 +157,26 @@ def text_files(path):
 
 def validate_args(path=None, bpe=None, batch_size=None, max_seq_length=512, mode='full',
                   mlm_probability=0.15, whole_word_masking=False, span=None, rank=None,
-                  world=None, round_bytes=32 << 20, special_ids=None, bpe_tables=None, **kw):
+                  world=None, round_bytes=32 << 20, special_ids=None, bpe_tables=None,
+                  unigram=None, unigram_tables=None, **kw):
     """Every argument error of get_roberta_pretrain_data_loader, raised before the GPU is
-    touched. Returns the files. bpe_tables takes the parsed (tokens, vocab, merges)."""
+    touched. Returns the files. bpe_tables takes the parsed (tokens, vocab, merges) of bpe=,
+    unigram_tables what `lddl_amd.unigram.load_model` reads from unigram=."""
     files = text_files(path)
-    if not isinstance(bpe, (tuple, list)) or len(bpe) != 2:
-        raise ValueError('bpe must be (vocab_json, merges_txt), not {!r}'.format(bpe))
-    from ..bpe import load_tables
-    tables = load_tables(*bpe)
-    if bpe_tables is not None:
-        bpe_tables[:] = tables
+    if unigram is not None:
+        if bpe is not None:
+            raise ValueError('pass bpe= or unigram=, not both')
+        from ..unigram import load_model
+        tables = load_model(unigram)
+        if unigram_tables is not None:
+            unigram_tables[:] = tables
+    else:
+        if not isinstance(bpe, (tuple, list)) or len(bpe) != 2:
+            raise ValueError('bpe must be (vocab_json, merges_txt), not {!r}'.format(bpe))
+        from ..bpe import load_tables
+        tables = load_tables(*bpe)
+        if bpe_tables is not None:
+            bpe_tables[:] = tables
     if not isinstance(batch_size, int) or isinstance(batch_size, bool) or batch_size < 1:
         raise ValueError('batch_size must be a positive int')
     _seq_len(max_seq_length)
@@ -184,8 +195,9 @@ class RobertaPretrainLoader:
     """The iterable get_roberta_pretrain_data_loader returns; each iter() is one epoch."""
 
     def __init__(self, **kw):
-        self._bpe_tables = []
-        self.files = validate_args(bpe_tables=self._bpe_tables, **kw)
+        self._bpe_tables, self._unigram_tables = [], []
+        self.files = validate_args(bpe_tables=self._bpe_tables,
+                                   unigram_tables=self._unigram_tables, **kw)
         self._kw = kw
         self._epoch = kw['start_epoch']
         self._ctx = None
@@ -201,8 +213,13 @@ class RobertaPretrainLoader:
         kw = self._kw
         self.rank, self.world = (get_rank(), get_world_size()) if kw['rank'] is None else \
             (kw['rank'], kw['world'])
-        self.bpe = BpeContext.from_tables(self._bpe_tables[0], self._bpe_tables[2],
-                                          vocab=self._bpe_tables[1])
+        if self._unigram_tables:  # the tokenizer's context, whichever of the two it is
+            from ..unigram import UnigramContext
+            p, sc, ty, unk, ws = self._unigram_tables
+            self.bpe = UnigramContext.from_tables(p, sc, ty, unk, ws)
+        else:
+            self.bpe = BpeContext.from_tables(self._bpe_tables[0], self._bpe_tables[2],
+                                              vocab=self._bpe_tables[1])
         # Punkt's tables live in a Context of the packaged WordPiece vocabulary, which here only
         # segments (as in the BART loader with bpe=)
         self._ctx = Context(os.path.join(ASSETS, 'vocab_synth_uncased_30522.txt'))
@@ -287,7 +304,8 @@ def get_roberta_pretrain_data_loader(path, bpe=None, batch_size=None, max_seq_le
                                      mode='full', mlm_probability=0.15, whole_word_masking=False,
                                      span=None, ignore_index=-100, base_seed=12345, start_epoch=0,
                                      rank=None, world=None, drop_last=False, round_bytes=32 << 20,
-                                     max_pieces=512, punkt_params=None, special_ids=None):
+                                     max_pieces=512, punkt_params=None, special_ids=None,
+                                     unigram=None):
     """RoBERTa pretraining batches from the text files (*.txt, one document per line) under
     `path` (past the reference, which has no RoBERTa loader). One process, one
     stream, no DataLoader workers: a round of files (at most round_bytes; this rank's are
@@ -297,5 +315,8 @@ def get_roberta_pretrain_data_loader(path, bpe=None, batch_size=None, max_seq_le
     permutation cuts the blocks into batches, and each step is one collate_blocks call with
     counter = (epoch << 32) | step. Yields dicts of int64 [batch, max_seq_length] input_ids,
     attention_mask and labels; the specials are the vocabulary's <s>, </s>, <pad> and <mask>
-    (special_ids overrides them). The ranks do not agree on a number of steps."""
+    (special_ids overrides them). unigram=model_file in place of bpe=: the sentences are
+    tokenized by the SentencePiece unigram model of an XLM-R / T5 checkpoint
+    (`lddl_amd.unigram.UnigramContext`); exactly one of the two is given. The
+    ranks do not agree on a number of steps."""
     return RobertaPretrainLoader(**dict(locals()))

@@ -107,8 +107,10 @@ def t5_corrupt(bpe_or_ctx, table, plan, rows=None, noise=(0, 0), noise_density=0
     from .._native import check, lib
     from ..bpe import BpeContext
     from ..context import _ptr, _stream
+    from ..unigram import UnigramContext
     ctx, sp = bpe_or_ctx, dict(special_ids or {})
-    names = ('</s>', '<pad>') if isinstance(ctx, BpeContext) else ('[SEP]', '[PAD]')
+    names = ('</s>', '<pad>') if isinstance(ctx, (BpeContext, UnigramContext)) else \
+        ('[SEP]', '[PAD]')
     eos, pad = (int(sp[k]) if k in sp else ctx.special_ids.get(n, -1)
                 for k, n in zip(('eos_id', 'pad_id'), names))
     if min(eos, pad) < 0:
@@ -162,11 +164,13 @@ def get_t5_pretrain_data_loader(path, bpe=None, batch_size=None, max_seq_length=
                                 noise_density=0.15, mean_noise_span_length=3.0, n_sentinels=100,
                                 ignore_index=-100, base_seed=12345, start_epoch=0, rank=None,
                                 world=None, drop_last=False, round_bytes=32 << 20, max_pieces=512,
-                                punkt_params=None, special_ids=None):
+                                punkt_params=None, special_ids=None, unigram=None):
     """T5 pretraining batches from the text files (*.txt, one document per line) under `path`
     (past the reference): get_roberta_pretrain_data_loader's rounds, tokenizer and
     block cut, with blocks of t5_tokens_length(max_seq_length) tokens, so that the encoder input
     of a full block is max_seq_length wide, and one t5_corrupt call per step with noise =
     (the rank's seed, (epoch << 32) | step). Yields t5_corrupt's dicts at the fixed widths
-    t5_lengths gives for that block length: every batch of a run has the same two shapes."""
+    t5_lengths gives for that block length: every batch of a run has the same two shapes.
+    unigram=model_file in place of bpe=: the ids are those of a T5 checkpoint's spiece.model
+    (DESIGN §32), and on its 32,000 pieces the default sentinels end at <extra_id_0> = 32099."""
     return T5PretrainLoader(**dict(locals()))
