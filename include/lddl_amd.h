@@ -998,9 +998,10 @@ int lddl_bpe_pretoken_stats(lddl_bpe* bpe, void* stream, const uint8_t* d_text, 
  * 10.0f. The path is read back from best[n]; consecutive unk_id pieces fuse into one. There is
  * no other floating point. The score of a USER_DEFINED piece is read as given (lddl_amd.unigram
  * passes SentencePiece's length * max score - 0.1 for them).
- * Deviations. The model's normaliser (nmt_nfkc and so on) is not applied beyond the space
- * classes: text it would change is tokenized as it stands. Byte fallback is not built; CONTROL,
- * UNKNOWN, UNUSED and BYTE pieces never match text. A word of more than LDDL_UNIGRAM_MAX_WORD
+ * Deviations. This call applies no normaliser beyond the space classes and tokenizes the text
+ * it is given (lddl_unigram_normalize_plan / _write below apply the model's rules first);
+ * CONTROL, UNKNOWN, UNUSED and BYTE pieces never match text (byte fallback, below, rewrites the
+ * finished path). A word of more than LDDL_UNIGRAM_MAX_WORD
  * bytes is encoded in consecutive slices of at most that many of its bytes, each cut at the
  * last character start that fits, each with a Viterbi and an unknown fusion of its own; only
  * the first slice carries the mark.
@@ -1048,6 +1049,78 @@ int lddl_unigram_tokenize(lddl_unigram* unigram, void* stream, const uint8_t* d_
 int lddl_unigram_word_stats(lddl_unigram* unigram, void* stream, const uint8_t* d_text,
                             int64_t n_bytes, const int64_t* d_sent_off, int64_t n_sent,
                             const int64_t* d_doc_sent_off, int64_t n_doc, int64_t* d_stats);
+
+/* ---------------------------------------------------------------------------------------------
+ * SentencePiece unigram: the model's normaliser and byte fallback. Both are off on
+ * a new lddl_unigram, which then behaves as stated above, bit for bit.
+ *
+ * Normaliser. A rule is (key, replacement), two byte strings; the rules are the enumerated
+ * precompiled_charsmap of the model (lddl_amd.unigram.load_normalizer). The pass follows
+ * SentencePiece's Normalizer::Normalize at add_dummy_prefix = remove_extra_whitespaces =
+ * escape_whitespaces = true. Per sentence, left to right from its first byte, at position i:
+ *   - the longest key that equals the bytes at i and ends inside the sentence: its replacement
+ *     (it may be empty) is emitted and i advances by the key's length;
+ *   - else, if a well-formed UTF-8 character starts at i and ends inside the sentence (no
+ *     overlong form, no surrogate, at most U+10FFFF), it is emitted unchanged and i advances by
+ *     its length;
+ *   - else EF BF BD (U+FFFD) is emitted and i advances by one byte.
+ * The scan is greedy and sequential: a position inside a consumed key is never a start, and no
+ * match crosses a sentence's end. Spaces in the output are not collapsed, stripped or escaped
+ * here: lddl_unigram_tokenize splits on runs of spaces and prefixes every word with the mark,
+ * so a replacement by a space, or by nothing, needs no more. While a normaliser is set,
+ * LDDL_UNIGRAM_ASCII_WS is ignored by lddl_unigram_tokenize and lddl_unigram_word_stats: the
+ * rules decide what becomes a space. Stated departure: a replacement with two interior spaces
+ * gives SentencePiece a piece that is the mark alone; here the spaces collapse.
+ * lddl_unigram_set_normalizer: rule r is key_blob[key_off[r] .. key_off[r + 1]) ->
+ * repl_blob[repl_off[r] .. repl_off[r + 1]), host arrays; n_rules = 0 turns the normaliser off
+ * (the arrays are unread). Fails with -1 on a NULL array, an empty key, a key of more than
+ * LDDL_UNIGRAM_NORM_MAX_KEY bytes (a key spans two 64-byte tiles at most, and up to that length
+ * no key makes a tile of plain text wait for the tile before it), a repeated key, more
+ * than 2^24 rules or offsets that do not rise from 0. It builds a byte trie of the keys in the
+ * layout of the pieces' trie, a (offset, length) pair per rule, the replacement blob and the
+ * masks of the bytes and byte pairs that start a key. It waits for the device (a set-up call).
+ * lddl_unigram_normalize_plan: asynchronous on `stream`, no host wait. Writes
+ * d_out_sent_off[n_sent + 1] (int64), the sentence offsets of the normalised text; the last
+ * entry is its size. d_sent_off rises from 0 to n_bytes. The plan's per-tile temporaries (17
+ * bytes per 64 of text, from the lddl_unigram's arena) stay until the next plan.
+ * lddl_unigram_normalize_write: asynchronous, no host wait; must follow the plan of the same
+ * d_text, n_bytes, d_sent_off and n_sent on the same lddl_unigram and the same stream (-1
+ * otherwise: the plan's temporaries return to the arena on the plan's stream), with
+ * d_out_sent_off as the plan wrote it, and writes the normalised text to d_out_text[out_cap].
+ * Fails with -1 and a message if out_cap is below the planned size, which it knows without
+ * waiting once the caller has waited for the plan (as a caller that sized d_out_text by
+ * d_out_sent_off[n_sent] has); in any case no byte is stored at or past out_cap.
+ *
+ * Byte fallback. lddl_unigram_set_byte_pieces(ids256): ids256[b] is the piece of byte b (the
+ * BYTE pieces <0x00> .. <0xFF> of the model), a host array; NULL turns it off. -1 on an id
+ * outside the vocabulary. It runs after the Viterbi, which is unchanged and still scores an
+ * unknown character at unk_score: every unk_id piece of the finished path is replaced by one
+ * piece per byte of the fused run of unknown characters it stands for, ids256[byte] in byte
+ * order. Pieces per byte stay at most 1, so the d_ids layout and d_sent_len's bounds hold. The
+ * bitmap of lddl_unigram_cont_bits gets the bits of the 256 ids: a byte piece always follows
+ * the mark or another piece of its word, which holds because lddl_unigram_create requires the
+ * mark to be a piece of its own, so that an unknown character never opens a word's pieces.
+ * lddl_unigram_cont_bits_host copies that bitmap, (n_pieces + 31) / 32 words, to the host
+ * (it waits for the copy).
+ * lddl_unigram_normalize_stats: measurement aid on the plan's stream; d_stats (device int64[2])
+ * = the tiles of the last plan and those that take the dirty path.
+ * lddl_unigram_norm_info: the rules, the longest key and replacement in bytes, whether byte
+ * fallback is on; any pointer may be NULL.
+ * ------------------------------------------------------------------------------------------- */
+#define LDDL_UNIGRAM_NORM_MAX_KEY 61
+int lddl_unigram_set_normalizer(lddl_unigram* unigram, const uint8_t* key_blob, const int64_t* key_off,
+                                const uint8_t* repl_blob, const int64_t* repl_off, int64_t n_rules);
+int lddl_unigram_set_byte_pieces(lddl_unigram* unigram, const int32_t* ids256);
+int lddl_unigram_norm_info(const lddl_unigram* unigram, int64_t* n_rules, int32_t* max_key,
+                           int32_t* max_repl, int32_t* byte_fallback);
+int lddl_unigram_normalize_plan(lddl_unigram* unigram, void* stream, const uint8_t* d_text,
+                                int64_t n_bytes, const int64_t* d_sent_off, int64_t n_sent,
+                                int64_t* d_out_sent_off);
+int lddl_unigram_normalize_stats(lddl_unigram* unigram, void* stream, int64_t* d_stats);
+int lddl_unigram_cont_bits_host(const lddl_unigram* unigram, uint32_t* bits);
+int lddl_unigram_normalize_write(lddl_unigram* unigram, void* stream, const uint8_t* d_text,
+                                 int64_t n_bytes, const int64_t* d_sent_off, int64_t n_sent,
+                                 const int64_t* d_out_sent_off, uint8_t* d_out_text, int64_t out_cap);
 
 /* ---------------------------------------------------------------------------------------------
  * RoBERTa blocks (past the reference): rows of contiguous whole sentences without

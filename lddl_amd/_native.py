@@ -186,6 +186,14 @@ SIGNATURES = {
                                              c_i32, c_vp, c_vp]),
     'lddl_unigram_word_stats': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
                                                c_vp]),
+    'lddl_unigram_set_normalizer': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
+    'lddl_unigram_set_byte_pieces': (ctypes.c_int, [c_vp, c_vp]),
+    'lddl_unigram_norm_info': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'lddl_unigram_normalize_plan': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    'lddl_unigram_normalize_stats': (ctypes.c_int, [c_vp, c_vp, c_vp]),
+    'lddl_unigram_cont_bits_host': (ctypes.c_int, [c_vp, c_vp]),
+    'lddl_unigram_normalize_write': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp,
+                                                    c_vp, c_i64]),
     # RoBERTa blocks (lddl_amd/torch/roberta.py); a nullable const lddl_span_params* comes last
     'lddl_blocks_plan': (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp,
                                         c_vp, c_vp, c_vp]),

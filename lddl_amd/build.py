@@ -53,7 +53,8 @@ UNIT_FLAGS = {u: _NO_PACKED_FP32 for u in ('denoise.hip', 'bpe_split.hip', 'bpe_
                                            'bpe_api.hip', 'blocks_plan.hip',
                                            'blocks_collate.hip', 't5_corrupt.hip',
                                            'unigram_match.hip', 'unigram_viterbi.hip',
-                                           'unigram_api.hip')}
+                                           'unigram_api.hip', 'unigram_norm.hip',
+                                           'unigram_bytes.hip', 'unigram_norm_api.hip')}
 UNIT_FLAGS_ID = repr(sorted(UNIT_FLAGS.items()))
 
 

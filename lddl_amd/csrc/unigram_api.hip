@@ -11,17 +11,7 @@
 #include "device.h"
 #include "lddl_amd.h"
 #include "scan.h"
-#include "unigram.h"
-
-struct lddl_unigram {
-  int device = 0;
-  lddl::UniTables tab{};
-  lddl::UniSlot* d_slots = nullptr;
-  lddl::UniSlot* d_root = nullptr;
-  uint32_t* d_cont_bits = nullptr;
-  int64_t n_pieces = 0, n_nodes = 0, n_slots = 0;
-  lddl::DevArena arena;  // the temporaries of lddl_unigram_tokenize
-};
+#include "unigram_norm.h"
 
 namespace lddl {
 namespace {
@@ -106,6 +96,11 @@ __global__ void __launch_bounds__(256) uni_stats_kernel(UniWork W, unsigned long
 }
 
 void release(lddl_unigram* u) {
+  u->plan.reset();
+  unigram_norm_free(u);
+  (void)hipFree(u->d_byte_ids);
+  if (u->plan_done) (void)hipEventDestroy(u->plan_done);
+  if (u->h_total) (void)hipHostFree(u->h_total);
   (void)hipFree(u->d_slots);
   (void)hipFree(u->d_root);
   (void)hipFree(u->d_cont_bits);
@@ -143,6 +138,7 @@ extern "C" int lddl_unigram_create(int device, const uint8_t* piece_bytes, const
   u->n_pieces = n_pieces;
   u->n_nodes = H.n_nodes;
   u->n_slots = (int64_t)H.slots.size();
+  u->cont_host = H.cont_bits;
   int st = upload(&u->d_slots, H.slots.data(), H.slots.size() * sizeof(UniSlot));
   st = st ? st : upload(&u->d_root, H.root, sizeof(H.root));
   st = st ? st : upload(&u->d_cont_bits, H.cont_bits.data(), H.cont_bits.size() * sizeof(uint32_t));
@@ -194,6 +190,8 @@ extern "C" int lddl_unigram_tokenize(lddl_unigram* u, void* stream, const uint8_
   if (n_sent == 0) return 0;
   if ((n_bytes && !d_text) || !d_sent_off || !d_ids || !d_sent_len) LDDL_FAIL(-1, "null argument");
   hipStream_t st = as_stream(stream);
+  UniTables tab = u->tab;
+  if (u->norm.rule) tab.ascii_ws = 0;  // the rules decide what a space is
   UniWork W{};
   fill_work(&W, d_text, n_bytes, d_sent_off, n_sent);
   W.long_cap = n_bytes / 65 + 2;
@@ -216,13 +214,16 @@ extern "C" int lddl_unigram_tokenize(lddl_unigram* u, void* stream, const uint8_
   int64_t* scan_tmp = W.tile_base + nt;
   W.sent_base = scan_tmp + scratch;
   W.long_list = W.sent_base + n_sent + 1;
-  LDDL_HIP(unigram_launch_words(u->tab, W, clear_words, st));
-  LDDL_HIP(unigram_launch_tiles(u->tab, W, st));
-  LDDL_HIP(unigram_launch_long(u->tab, W, st));
+  LDDL_HIP(unigram_launch_words(tab, W, clear_words, st));
+  LDDL_HIP(unigram_launch_tiles(tab, W, st));
+  LDDL_HIP(unigram_launch_long(tab, W, st));
+  if (u->d_byte_ids) {  // tile_base is free until the scan: the cover words
+    LDDL_HIP(unigram_launch_bytes(tab, W, u->d_byte_ids, reinterpret_cast<uint64_t*>(W.tile_base), st));
+  }
   LDDL_HIP(scan_exclusive(TileCount{W.alive_bits, W.pre_bits}, W.n_tiles, W.tile_base, scan_tmp, st));
   hipLaunchKernelGGL(uni_sent_base_kernel, dim3((unsigned)(n_sent / 256 + 1)), dim3(256), 0, st, W);
   hipLaunchKernelGGL(uni_compact_kernel, dim3((unsigned)((W.n_tiles + 3) / 4)), dim3(256), 0, st, W,
-                     u->tab.pre_id, max_pieces, d_ids);
+                     tab.pre_id, max_pieces, d_ids);
   hipLaunchKernelGGL(uni_sent_len_kernel, dim3((unsigned)((n_sent + 255) / 256)), dim3(256), 0, st, W,
                      max_pieces, d_sent_len);
   LDDL_HIP(hipGetLastError());
@@ -248,7 +249,9 @@ extern "C" int lddl_unigram_word_stats(lddl_unigram* u, void* stream, const uint
   unsigned long long* counters = reinterpret_cast<unsigned long long*>(base + nt);
   W.start_bits = base + clear_words;
   W.break_bits = W.start_bits + nt;
-  LDDL_HIP(unigram_launch_words(u->tab, W, clear_words, st));
+  UniTables tab = u->tab;
+  if (u->norm.rule) tab.ascii_ws = 0;
+  LDDL_HIP(unigram_launch_words(tab, W, clear_words, st));
   hipLaunchKernelGGL(uni_stats_kernel, dim3((unsigned)((W.n_tiles + 255) / 256)), dim3(256), 0, st, W,
                      counters);
   LDDL_HIP(hipGetLastError());

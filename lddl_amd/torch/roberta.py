@@ -214,9 +214,11 @@ class RobertaPretrainLoader:
         self.rank, self.world = (get_rank(), get_world_size()) if kw['rank'] is None else \
             (kw['rank'], kw['world'])
         if self._unigram_tables:  # the tokenizer's context, whichever of the two it is
-            from ..unigram import UnigramContext
+            from ..unigram import UnigramContext, load_normalizer
             p, sc, ty, unk, ws = self._unigram_tables
-            self.bpe = UnigramContext.from_tables(p, sc, ty, unk, ws)
+            keys, repls, byte_pieces = load_normalizer(kw['unigram'])
+            self.bpe = UnigramContext.from_tables(p, sc, ty, unk, ws, byte_pieces=byte_pieces,
+                                                  normalizer=(keys, repls) if keys else None)
         else:
             self.bpe = BpeContext.from_tables(self._bpe_tables[0], self._bpe_tables[2],
                                               vocab=self._bpe_tables[1])
@@ -257,6 +259,8 @@ class RobertaPretrainLoader:
         doc_off = np.zeros(len(docs) + 1, np.int64)
         np.cumsum([len(d) for d in docs], out=doc_off[1:])
         sent_off, doc_sent_off = punkt.segment(self._ctx, text, torch.from_numpy(doc_off).to(dev))
+        if getattr(self.bpe, 'rules', 0):  # a unigram model's normaliser: the text it tokenizes
+            text, sent_off = self.bpe.normalize(text, sent_off)
         ids, sent_len = self.bpe.tokenize(text, sent_off, doc_sent_off, self._kw['max_pieces'])
         table = (ids, sent_off, sent_len, doc_sent_off)
         plan, n = roberta_blocks(table, self.plan_seq_len(), self._kw['mode'])

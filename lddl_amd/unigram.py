@@ -2,7 +2,8 @@
 XLM-R and mBART checkpoints, from their `spiece.model`. `load_model` reads the file with a
 protobuf wire reader of its own (no dependency on `sentencepiece` or `protobuf`),
 `UnigramContext` hands byte strings, scores and types to lddl_unigram_create and wraps
-lddl_unigram_tokenize (include/lddl_amd.h states the semantics). Argument errors are raised
+lddl_unigram_tokenize (include/lddl_amd.h states the semantics). `load_normalizer` reads the
+model's normalisation rules and byte pieces, which the context applies on the device (§33). Argument errors are raised
 before the native library is imported.
 """
 import os
@@ -97,6 +98,92 @@ def load_model(path):
     return pieces, scores, types, types.tolist().index(UNKNOWN), name != b'identity'
 
 
+def _charsmap_rules(cm):
+    """(keys, repls) of a precompiled_charsmap: a little-endian uint32 trie size, a Darts
+    double-array of uint32 units, a blob of NUL-terminated replacements. The keys come from a
+    bounds-checked walk of the array, breadth first, 255 labels of a level's nodes at a time."""
+    if len(cm) < 4:
+        raise ValueError('precompiled_charsmap: no trie size')
+    size = struct.unpack('<I', cm[:4])[0]
+    if size == 0 or size % 4 or 4 + size > len(cm):
+        raise ValueError('precompiled_charsmap: a trie of {} bytes in {}'.format(size, len(cm) - 4))
+    units = np.frombuffer(cm, '<u4', size // 4, 4).astype(np.int64)
+    blob, n = cm[4 + size:], size // 4
+    labels = np.arange(1, 256, dtype=np.int64)
+    nodes, keys, found, depth = np.zeros(1, np.int64), [b''], [], 0
+    while len(nodes):
+        u = units[nodes]
+        base = nodes ^ ((u >> 10) << ((u & 0x200) >> 6))
+        if (base >= n).any():
+            raise ValueError('precompiled_charsmap: a unit\'s offset leaves the array')
+        for i in np.flatnonzero((u >> 8) & 1):
+            if not keys[i]:
+                raise ValueError('precompiled_charsmap: an empty key')
+            found.append((keys[i], int(units[base[i]] & 0x7FFFFFFF)))
+        nxt, nxt_keys = [], []
+        for a in range(0, len(nodes), 4096):
+            cand = base[a:a + 4096, None] ^ labels[None, :]
+            ok = (cand < n) & ((units[np.minimum(cand, n - 1)] & 0x800000FF) == labels[None, :])
+            r, c = np.nonzero(ok)
+            nxt.append(cand[r, c])
+            nxt_keys += [keys[a + i] + bytes((j + 1,)) for i, j in zip(r.tolist(), c.tolist())]
+        nodes, keys = np.concatenate(nxt), nxt_keys
+        depth += 1  # Darts shares suffixes, so paths outnumber units; a cycle shows as depth
+        if depth > 256 or len(nodes) > 1 << 24:
+            raise ValueError('precompiled_charsmap: the array is no trie')
+    out_k, out_r = [], []
+    for k, v in sorted(found):
+        end = blob.find(b'\0', v) if v < len(blob) else -1
+        if end < 0:
+            raise ValueError('precompiled_charsmap: a value past the blob, or no terminator')
+        out_k.append(k)
+        out_r.append(blob[v:end])
+    return out_k, out_r
+
+
+def load_normalizer(path):
+    """(keys, repls, byte_pieces) of a SentencePiece model file: the rules of
+    normalizer_spec.precompiled_charsmap as two lists of bytes, sorted by key (an `identity`
+    model, or one without a map, has none), and the ids of the BYTE pieces <0x00> .. <0xFF> as
+    int32 [256], None unless all 256 are there. ValueError on a malformed map: an index that
+    leaves the array or the blob, an empty key, a replacement without its terminator."""
+    if not isinstance(path, str) or not os.path.isfile(path):
+        raise FileNotFoundError('model_file {!r}: a local file is required'.format(path))
+    with open(path, 'rb') as f:
+        raw = f.read()
+    cm, ids, i = b'', {}, 0
+    try:
+        for num, wt, val in _fields(raw):
+            if num == 1 and wt == 2:
+                p = {k: v for k, _, v in _fields(val)}
+                name = p.get(1, b'')
+                if p.get(3, NORMAL) == BYTE and len(name) == 6 and name[:3] == b'<0x' and name[5:] == b'>':
+                    ids[int(name[3:5], 16)] = i
+                i += 1
+            elif num == 3 and wt == 2:
+                for k, _, v in _fields(val):
+                    if k == 2:
+                        cm = v
+    except (struct.error, TypeError) as e:
+        raise ValueError('{}: not a SentencePiece model ({})'.format(path, e)) from None
+    keys, repls = _charsmap_rules(cm) if cm else ([], [])
+    return keys, repls, (np.array([ids[b] for b in range(256)], np.int32) if len(ids) == 256 else None)
+
+
+def check_normalizer(normalizer, byte_pieces):
+    """from_tables' normalizer=(keys, repls) and byte_pieces= as the native calls take them."""
+    if normalizer is not None:
+        keys, repls = ([k.encode('utf-8') if isinstance(k, str) else bytes(k) for k in x] for x in normalizer)
+        if len(keys) != len(repls) or not keys:
+            raise ValueError('normalizer: one replacement per key, one rule at least')
+        normalizer = (keys, repls)
+    if byte_pieces is not None:
+        byte_pieces = np.ascontiguousarray(byte_pieces, np.int32).reshape(-1)
+        if len(byte_pieces) != 256:
+            raise ValueError('byte_pieces must be 256 ids')
+    return normalizer, byte_pieces
+
+
 def check_tables(pieces, scores, types=None, unk_id=0):
     """from_tables' arguments as create_native takes them (ValueError on mismatched shapes)."""
     pieces = [p.encode('utf-8') if isinstance(p, str) else bytes(p) for p in pieces]
@@ -131,18 +218,23 @@ class UnigramContext:
     """A unigram vocabulary resident in HBM; kernels run on torch's current stream."""
 
     def __init__(self, model_file, device=None):
-        self._attach(*load_model(model_file), device)
+        tables = load_model(model_file)
+        keys, repls, byte_pieces = load_normalizer(model_file)
+        self._attach(*tables, device, (keys, repls) if keys else None, byte_pieces)
 
     @classmethod
-    def from_tables(cls, pieces, scores, types=None, unk_id=0, ascii_ws=False, device=None):
+    def from_tables(cls, pieces, scores, types=None, unk_id=0, ascii_ws=False, device=None,
+                    normalizer=None, byte_pieces=None):
         """A context of tables already in memory (hand-built, or load_model's): pieces (bytes or
         str by id), scores, types (None: all NORMAL but unk_id), as lddl_unigram_create takes
-        them."""
+        them. normalizer=(keys, repls), two lists of bytes or str, and byte_pieces, 256 ids, are
+        load_normalizer's; with both None the context is that of §32."""
         self = cls.__new__(cls)
-        self._attach(*check_tables(pieces, scores, types, unk_id), bool(ascii_ws), device)
+        tables = check_tables(pieces, scores, types, unk_id)
+        self._attach(*tables, bool(ascii_ws), device, *check_normalizer(normalizer, byte_pieces))
         return self
 
-    def _attach(self, pieces, scores, types, unk_id, ascii_ws, device):
+    def _attach(self, pieces, scores, types, unk_id, ascii_ws, device, normalizer=None, byte_pieces=None):
         self.pieces, self.scores, self.types = pieces, scores, types
         self.unk_id, self.ascii_ws = unk_id, ascii_ws
         names = {p: i for i, p in reversed(list(enumerate(pieces)))}
@@ -157,6 +249,17 @@ class UnigramContext:
         bits, n = ctypes.c_void_p(), ctypes.c_int64()
         check(lib.lddl_unigram_cont_bits(self._h, ctypes.byref(bits), ctypes.byref(n)))
         self.cont_bits = (bits, n.value)  # lddl_bart_denoise_bits' first two arguments
+        self.rules = 0
+        if normalizer is not None:
+            blobs = []
+            for strings in normalizer:
+                off = np.zeros(len(strings) + 1, np.int64)
+                np.cumsum([len(x) for x in strings], out=off[1:])
+                blobs += [np.frombuffer(b''.join(strings) + b'\0', np.uint8), off]
+            check(lib.lddl_unigram_set_normalizer(self._h, *(a.ctypes.data for a in blobs), len(normalizer[0])))
+            self.rules = len(normalizer[0])
+        if byte_pieces is not None:
+            check(lib.lddl_unigram_set_byte_pieces(self._h, byte_pieces.ctypes.data))
 
     @property
     def handle(self):
@@ -178,14 +281,49 @@ class UnigramContext:
             pass
 
     def info(self):
-        """lddl_unigram_info -> dict of pieces, nodes, table_bytes, unk_score, max_word."""
+        """lddl_unigram_info and lddl_unigram_norm_info -> dict of pieces, nodes, table_bytes,
+        unk_score, max_word; rules, max_key, max_repl (bytes), byte_fallback."""
         import ctypes
         from ._native import check, lib
         a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         u, w = ctypes.c_float(), ctypes.c_int32()
         check(lib.lddl_unigram_info(self._h, *(ctypes.addressof(v) for v in (a, b, c, u, w))))
+        r, k, m, f = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        check(lib.lddl_unigram_norm_info(self._h, *(ctypes.addressof(v) for v in (r, k, m, f))))
         return {'pieces': a.value, 'nodes': b.value, 'table_bytes': c.value, 'unk_score': u.value,
-                'max_word': w.value}
+                'max_word': w.value, 'rules': r.value, 'max_key': k.value, 'max_repl': m.value,
+                'byte_fallback': bool(f.value)}
+
+    def continuation_ids(self):
+        """The ids whose bit is set in the continuation bitmap (lddl_unigram_cont_bits): the
+        pieces that never begin a word."""
+        from ._native import check, lib
+        bits = np.zeros((len(self.pieces) + 31) // 32, np.uint32)
+        check(lib.lddl_unigram_cont_bits_host(self._h, bits.ctypes.data))
+        return [i for i in range(len(self.pieces)) if bits[i >> 5] >> np.uint32(i & 31) & 1]
+
+    def normalize(self, text, sent_off, out_cap=None):
+        """The model's normaliser on tokenize's input -> (text2, sent_off2), the
+        input itself if no normaliser is set. lddl_unigram_normalize_plan, one read-back of the
+        planned size (the one host wait: the output is allocated by it), then
+        lddl_unigram_normalize_write. out_cap: the capacity handed to the write instead of the
+        planned size (NativeError if it is too small)."""
+        import torch
+        from ._native import check, lib
+        from .context import _ptr, _stream
+        if not self.rules:
+            return text, sent_off
+        assert text.dtype == torch.uint8 and text.is_cuda and text.is_contiguous()
+        assert sent_off.dtype == torch.int64 and sent_off.is_cuda and sent_off.is_contiguous()
+        n_sent = sent_off.numel() - 1
+        so2 = torch.empty(n_sent + 1, dtype=torch.int64, device=self.device)
+        head = (self._h, _stream(), _ptr(text), text.numel(), _ptr(sent_off), n_sent, _ptr(so2))
+        check(lib.lddl_unigram_normalize_plan(*head))
+        size = int(so2[-1].item())
+        cap = size if out_cap is None else int(out_cap)
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device)
+        check(lib.lddl_unigram_normalize_write(*head, _ptr(out), cap))
+        return out[:size], so2
 
     def _call(self, fn, text, sent_off, doc_sent_off, *tail):
         import torch
@@ -224,16 +362,17 @@ class UnigramContext:
         return out
 
     def tokenize_host(self, text, sent_off, doc_sent_off=None, max_pieces=512):
-        """Convenience: numpy in, ragged numpy (ids, offsets) out."""
+        """Convenience: numpy in, ragged numpy (ids, offsets) out; normalised first if a
+        normaliser is set."""
         import torch
         dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(self.device)  # noqa: E731
-        ids, sl = self.tokenize(dev(text, np.uint8), dev(sent_off, np.int64),
-                                None if doc_sent_off is None else dev(doc_sent_off, np.int64),
+        text, so = self.normalize(dev(text, np.uint8), dev(sent_off, np.int64))
+        ids, sl = self.tokenize(text, so, None if doc_sent_off is None else dev(doc_sent_off, np.int64),
                                 max_pieces)
         ids, sl = ids.cpu().numpy(), sl.cpu().numpy().astype(np.int64)
         out_off = np.zeros(len(sl) + 1, np.int64)
         np.cumsum(sl, out=out_off[1:])
-        so = np.asarray(sent_off, np.int64)
+        so = so.cpu().numpy()
         flat = [ids[so[i]:so[i] + sl[i]] for i in range(len(sl))]
         return (np.concatenate(flat) if flat else np.zeros(0, np.int32)), out_off
 
@@ -244,7 +383,7 @@ class UnigramContext:
         b = np.frombuffer(s.encode('utf-8'), np.uint8)
         if not len(b):
             return []
-        return self.tokenize_host(b, [0, len(b)], None, len(b))[0].tolist()
+        return self.tokenize_host(b, [0, len(b)], None, 1 << 30)[0].tolist()
 
     def convert_ids_to_tokens(self, ids):
         """Ids -> the piece strings of the model."""
