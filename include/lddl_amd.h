@@ -1259,6 +1259,98 @@ int lddl_t5_corrupt(void* stream, const int32_t* d_ids, const int64_t* d_sent_of
                     int64_t* d_labels, int64_t* d_decoder_input_ids, int64_t* d_src_lengths,
                     int64_t* d_tgt_lengths);
 
+/* ---------------------------------------------------------------------------------------------
+ * The GPT stream (past the reference): rows for causal language modelling, cut from
+ * one endless stream doc, eos, doc, eos, ... of the round's documents; Megatron-LM's GPT dataset
+ * with reset_position_ids / eod_mask_loss, and the document-level fill-in-the-middle transform
+ * of Bavarian et al. 2022 applied before packing. A row starts and ends anywhere inside a
+ * document and no slot is padded. The input is a token table as lddl_tokenize and
+ * lddl_bpe_tokenize lay it out: d_ids, d_sent_off[n_sent + 1], d_sent_len[n_sent] (len(s) =
+ * d_sent_len[s] & (2^30 - 1); gaps between sentences allowed) and d_doc_sent_off[n_doc + 1]. A
+ * document's tokens are the concatenated pieces of its sentences, t(d) of them, fewer than
+ * 2^31 - 4.
+ *   order   d_doc_order, an int64 permutation of [0, n_doc) on the device, or NULL for the
+ *     identity: the stream takes document d_doc_order[j] at place j (the caller's to check; an
+ *     id outside is clamped).
+ *   FIM     per document r = the Philox call of lddl_mask_dynamic at index d, the document's id
+ *     in the table (not its place, so the shuffle does not change a document's transform),
+ *     under seed and counter. fim_q and spm_q are the two rates in 16.16 fixed point, rounded
+ *     half up by the caller, in [0, 65536]. A document with t >= 1 is transformed iff
+ *     (r.x >> 16) < fim_q; it takes the SPM layout iff it is transformed and (r.y >> 16) <
+ *     spm_q, else PSM. The cuts a <= b are the sorted pair (r.z * (t + 1)) >> 32, (r.w *
+ *     (t + 1)) >> 32, both in [0, t]. With prefix = [0, a), middle = [a, b), suffix = [b, t):
+ *       PSM  fim_prefix_id prefix fim_suffix_id suffix fim_middle_id middle
+ *       SPM  fim_prefix_id fim_suffix_id suffix fim_middle_id prefix middle
+ *     Either adds 3 tokens; empty pieces are legal; t = 0 is never transformed. The cuts are
+ *     token-level: the stated deviation from the paper's character-level cuts.
+ *   stream  cost(d) = t(d) + 1, + 3 when transformed: the + 1 is the terminator eos_id behind
+ *     every document, also behind an empty one (a second deviation, from loaders that drop
+ *     empty documents), so document offsets rise strictly. Q = the int64 exclusive prefix sum
+ *     of cost(d_doc_order[j]) over the places, Q[n_doc] the total. n_rows = max(0, (Q[n_doc] -
+ *     1) / L), L = seq_len; row r reads stream positions r * L .. r * L + L, and the tail that
+ *     fills no row is dropped.
+ *
+ * lddl_stream_plan writes d_sent_tok_off[n_sent + 1], the exclusive prefix sum of len(s),
+ * d_doc_off[n_doc + 1] = Q, and d_n_rows[0] = n_rows, d_n_rows[1] = Q[n_doc]. Asynchronous on
+ * `stream`, no host wait (the caller reads d_n_rows once per plan), no atomics; the scans'
+ * scratch comes from an arena that the library keeps per device and lddl_stream_release()
+ * empties. No record of the draws is kept: lddl_stream_rows draws them again from the same
+ * seed and counter.
+ *
+ * lddl_stream_rows: output row i is plan row d_rows[i] (NULL: row i; an index outside [0,
+ * n_rows) is clamped into it), slot y in [0, L), all int64 [batch, seq_len]:
+ *   input_ids[y]    stream token r * L + y.
+ *   labels[y]       stream token r * L + y + 1; with eod_mask_loss, ignore_index where the
+ *     slot's input is a document's terminator, decided by its position in the stream, not by
+ *     comparing ids.
+ *   position_ids[y] y minus the slot of the last sequence start at or before y, where the
+ *     row's slot 0 is always a start and so is a slot whose predecessor is a terminator;
+ *     without reset_position_ids it is y.
+ *   sequence_ids[y] the number of terminators in the row's slots before y.
+ * There is no attention mask: every slot is real. Every element is written exactly once; one
+ * launch, workgroups of LDDL_STREAM_TILE slots, no temporaries, no atomics. A tile that
+ * overlaps more than LDDL_STREAM_LDS_DOCS places is served from global memory past that many.
+ * The knobs (d_doc_order, fim_q, spm_q, seed, counter) must be the plan's. A plan without a
+ * row (or n_doc = 0) writes nothing.
+ *
+ * lddl_stream_cu_seqlens: d_cu_seqlens int32 [max_seqs + 1] and d_n_seqs int32 [1] for
+ * variable-length attention that does not cross documents: the flat offsets i * L + y of every
+ * sequence start of the batch in order (slot 0 of each row, every slot y >= 1 whose
+ * predecessor is a terminator). cu_seqlens[n_seqs] and everything behind it is batch * L;
+ * n_seqs is the untruncated count. If n_seqs > max_seqs, the first max_seqs starts are written
+ * and cu_seqlens[max_seqs] = batch * L, so the caller sees the overflow by n_seqs. A row holds
+ * its own start and one start per document that begins inside it, and a document begins once
+ * in the stream: a batch of distinct rows has at most batch + n_doc starts and at most batch *
+ * L, so max_seqs = min(batch * L, batch + n_doc) cannot overflow (with repeated rows,
+ * min(batch * L, batch * (1 + n_doc))). One workgroup, one launch.
+ *
+ * All three fail with -1 before anything is launched on seq_len outside [1, 2^20], a negative
+ * size, and a NULL array of non-zero size; the plan and the rows on a rate outside [0, 65536];
+ * the rows on a negative eos_id and on fim_q > 0 with any of the three sentinel ids negative;
+ * lddl_stream_cu_seqlens on max_seqs < 1 and batch * seq_len > 2^31 - 1. batch = 0 writes no
+ * row.
+ * ------------------------------------------------------------------------------------------- */
+#define LDDL_STREAM_TILE 1024
+#define LDDL_STREAM_LDS_DOCS 256
+int lddl_stream_plan(void* stream, const int32_t* d_sent_len, int64_t n_sent,
+                     const int64_t* d_doc_sent_off, int64_t n_doc, const int64_t* d_doc_order,
+                     int32_t seq_len, int32_t fim_q, int32_t spm_q, uint64_t seed,
+                     uint64_t counter, int64_t* d_sent_tok_off, int64_t* d_doc_off,
+                     int64_t* d_n_rows);
+int lddl_stream_release(void);
+int lddl_stream_rows(void* stream, const int32_t* d_ids, const int64_t* d_sent_off,
+                     int64_t n_sent, const int64_t* d_doc_sent_off, int64_t n_doc,
+                     const int64_t* d_doc_order, const int64_t* d_sent_tok_off,
+                     const int64_t* d_doc_off, const int64_t* d_rows, int32_t batch,
+                     int32_t seq_len, int32_t fim_q, int32_t spm_q, uint64_t seed,
+                     uint64_t counter, int64_t eos_id, int64_t fim_prefix_id,
+                     int64_t fim_middle_id, int64_t fim_suffix_id, int32_t eod_mask_loss,
+                     int32_t reset_position_ids, int64_t ignore_index, int64_t* d_input_ids,
+                     int64_t* d_labels, int64_t* d_position_ids, int64_t* d_sequence_ids);
+int lddl_stream_cu_seqlens(void* stream, const int64_t* d_doc_off, int64_t n_doc,
+                           const int64_t* d_rows, int32_t batch, int32_t seq_len,
+                           int32_t max_seqs, int32_t* d_cu_seqlens, int32_t* d_n_seqs);
+
 #ifdef __cplusplus
 }
 #endif

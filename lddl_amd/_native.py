@@ -210,6 +210,16 @@ SIGNATURES = {
                                        c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64,
                                        c_i64, c_i64, c_u64, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                        c_vp]),
+    # the GPT stream (lddl_amd/torch/gpt.py)
+    'lddl_stream_plan': (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32,
+                                        c_u64, c_u64, c_vp, c_vp, c_vp]),
+    'lddl_stream_release': (ctypes.c_int, []),
+    'lddl_stream_rows': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                        c_vp, c_i32, c_i32, c_i32, c_i32, c_u64, c_u64, c_i64,
+                                        c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp,
+                                        c_vp]),
+    'lddl_stream_cu_seqlens': (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp,
+                                              c_vp]),
 }
 
 

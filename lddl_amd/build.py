@@ -54,7 +54,8 @@ UNIT_FLAGS = {u: _NO_PACKED_FP32 for u in ('denoise.hip', 'bpe_split.hip', 'bpe_
                                            'blocks_collate.hip', 't5_corrupt.hip',
                                            'unigram_match.hip', 'unigram_viterbi.hip',
                                            'unigram_api.hip', 'unigram_norm.hip',
-                                           'unigram_bytes.hip', 'unigram_norm_api.hip')}
+                                           'unigram_bytes.hip', 'unigram_norm_api.hip',
+                                           'stream_plan.hip', 'stream_rows.hip')}
 UNIT_FLAGS_ID = repr(sorted(UNIT_FLAGS.items()))
 
 

@@ -9,7 +9,9 @@ denoising (`bart_denoise`, `get_bart_pretrain_data_loader`; past the reference) 
 loader (`roberta_blocks`, `collate_blocks`, `get_roberta_pretrain_data_loader`: FULL- and
 DOC-SENTENCES blocks cut and collated on the device; past the reference) and T5 span corruption
 (`t5_corrupt`, `t5_lengths`, `t5_tokens_length`, `get_t5_pretrain_data_loader`: exact-count
-spans and sentinel rows from the same blocks; past the reference) are resolved lazily, so that DataLoader workers started with `spawn` / `forkserver` import only the
+spans and sentinel rows from the same blocks; past the reference) and the GPT loader
+(`stream_plan`, `collate_stream`, `get_gpt_pretrain_data_loader`: documents packed across rows
+for causal language modelling, with optional fill-in-the-middle; past the reference) are resolved lazily, so that DataLoader workers started with `spawn` / `forkserver` import only the
 worker-side modules (`packing`, `seqpack`, `datasets`), never the native library."""
 
 
@@ -34,4 +36,7 @@ def __getattr__(name):
     if name in ('t5_lengths', 't5_tokens_length', 't5_corrupt', 'get_t5_pretrain_data_loader'):
         from . import t5
         return getattr(t5, name)
+    if name in ('stream_plan', 'collate_stream', 'get_gpt_pretrain_data_loader'):
+        from . import gpt
+        return getattr(gpt, name)
     raise AttributeError(name)
