@@ -950,6 +950,41 @@ int lddl_bart_denoise_bits(const uint32_t* d_cont_bits, int64_t n_ids, void* str
  * per byte of text) come from an arena the lddl_bpe owns and are reused by the next call.
  * Fails with -1 on a NULL lddl_bpe, a negative size, max_pieces < 1, or, with n_sent > 0, a
  * NULL array; n_sent = 0 launches nothing.
+ *
+ * The cl100k pattern (Llama 3, GPT-4, Qwen2 / 2.5, DeepSeek).
+ * lddl_bpe_set_pattern(bpe, "cl100k", digit_group) makes lddl_bpe_tokenize and
+ * lddl_bpe_pretoken_stats cut a document by
+ *   (?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ * with digit_group 3, and with \p{N} in place of \p{N}{1,3} (Qwen2) with digit_group 1: what
+ * Python's `regex.findall` returns. Documents, classes, \s and ill-formed bytes as above; the
+ * contraction letters match ASCII in either case, and U+017F (long s) counts as s. Stated as
+ * rules (csrc/bpe_split_cl.hip):
+ *   digit       the k-th character (from 0) of a maximal run of digits starts a pre-token iff
+ *               k % digit_group == 0; nothing absorbs a run's first digit.
+ *   other       starts iff the character before is neither "other" nor U+0020 (the U+0020
+ *               opened the token). An apostrophe that starts and is followed by a contraction
+ *               fires: the contraction is a pre-token and the character behind it starts.
+ *   letter      the first letter of a run starts unless the character before absorbs it: a
+ *               starting "other" that did not fire ("(b" is one pre-token, "((b" is "((", "b"),
+ *               or white space other than \r and \n ("a\xa0b" is "a", "\xa0b").
+ *   white space of a maximal run M: the newlines at M's head that directly follow an "other"
+ *               belong to that pre-token. The rest W starts at its first character; if W holds
+ *               a newline, that pre-token runs to W's last newline. The remainder R starts at
+ *               its first character, and if R has two characters or more and a character
+ *               follows the run, R's last character starts as well (it goes with a following
+ *               letter, with a following "other" if it is U+0020, and is a pre-token by itself
+ *               otherwise). At a document's end R is one pre-token.
+ * "gpt2" with digit_group 0 restores the default. Fails with -1 on any other pattern or
+ * digit_group.
+ * lddl_bpe_set_whole_words(bpe, 1): `ignore_merges` of a Hugging Face tokenizer.json (Llama 3
+ * sets it). After the split, a pre-token of 2 to LDDL_BPE_MAX_WORD bytes whose bytes equal a
+ * vocabulary entry is that one id (the lowest of equal entries); for every other pre-token the
+ * merges decide. 0 restores the default; any other value fails with -1.
+ * Both settings hold for the calls issued after them; the temporaries of the cl100k split are
+ * 3 bytes per 64 bytes of text more. lddl_bpe_create builds the whole-word table for every
+ * lddl_bpe, set or not: 16 bytes per slot (a power of two, at least twice the tokens of 2 bytes
+ * and more), a copy of token_bytes and of token_off on the device; about 6 MB for a vocabulary
+ * of 128k tokens.
  * ------------------------------------------------------------------------------------------- */
 #define LDDL_BPE_MAX_WORD 1024
 typedef struct lddl_bpe lddl_bpe;
@@ -960,6 +995,8 @@ int lddl_bpe_destroy(lddl_bpe* bpe);
 int lddl_bpe_info(const lddl_bpe* bpe, int64_t* n_tokens, int64_t* n_merges,
                   int32_t* unicode_version, int32_t* max_word);
 int lddl_bpe_cont_bits(const lddl_bpe* bpe, const uint32_t** d_bits, int64_t* n_ids);
+int lddl_bpe_set_pattern(lddl_bpe* bpe, const char* pattern, int32_t digit_group);
+int lddl_bpe_set_whole_words(lddl_bpe* bpe, int32_t on);
 int lddl_bpe_tokenize(lddl_bpe* bpe, void* stream, const uint8_t* d_text, int64_t n_bytes,
                       const int64_t* d_sent_off, int64_t n_sent, const int64_t* d_doc_sent_off,
                       int64_t n_doc, int32_t max_pieces, int32_t* d_ids, int32_t* d_sent_len);

@@ -172,6 +172,8 @@ SIGNATURES = {
     'lddl_bpe_destroy': (ctypes.c_int, [c_vp]),
     'lddl_bpe_info': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     'lddl_bpe_cont_bits': (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
+    'lddl_bpe_set_pattern': (ctypes.c_int, [c_vp, ctypes.c_char_p, c_i32]),
+    'lddl_bpe_set_whole_words': (ctypes.c_int, [c_vp, c_i32]),
     'lddl_bpe_tokenize': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32,
                                          c_vp, c_vp]),
     'lddl_bpe_pretoken_stats': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,

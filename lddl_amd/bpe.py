@@ -2,7 +2,9 @@
 checkpoints share, from `vocab.json` and `merges.txt`. `BpeContext` undoes JSON and GPT-2's
 byte-to-unicode map, hands raw byte strings and (left, right, merged) id triples in rank order
 to lddl_bpe_create, and wraps lddl_bpe_tokenize (include/lddl_amd.h states the semantics).
-Argument errors are raised before the native library is imported.
+pattern='cl100k' / 'qwen2' and ignore_merges=True give the ids of Llama 3, GPT-4,
+Qwen2 and DeepSeek checkpoints; `BpeContext.from_tokenizer_json` reads all of it from a Hugging
+Face tokenizer.json. Argument errors are raised before the native library is imported.
 """
 import json
 import os
@@ -15,6 +17,32 @@ SYNTH_VOCAB = os.path.join(ASSETS, 'bpe_synth_vocab.json')
 SYNTH_MERGES = os.path.join(ASSETS, 'bpe_synth_merges.txt')
 SPECIALS = ('<s>', '<pad>', '</s>', '<unk>', '<mask>')
 MAX_WORD = 1024  # LDDL_BPE_MAX_WORD
+# pattern -> (lddl_bpe_set_pattern's name, its digit_group when none is given)
+PATTERNS = {'gpt2': ('gpt2', 0), 'cl100k': ('cl100k', 3), 'qwen2': ('cl100k', 1)}
+_CL = (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}%s| ?[^\s\p{L}\p{N}]+[\r\n]*"
+       r"|\s*[\r\n]+|\s+(?!\S)|\s+")
+# the regex strings of a tokenizer.json's Split pre-tokenizer that from_tokenizer_json knows
+SPLIT_REGEX = {
+    r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+": 'gpt2',
+    _CL % '{1,3}': 'cl100k',
+    _CL % '': 'qwen2',
+}
+
+
+def check_options(pattern='gpt2', digit_group=None, ignore_merges=False):
+    """(lddl_bpe_set_pattern's name, digit_group, ignore_merges) of BpeContext's keywords, or a
+    ValueError."""
+    if pattern not in PATTERNS:
+        raise ValueError('pattern must be one of {}, not {!r}'.format(sorted(PATTERNS), pattern))
+    name, group = PATTERNS[pattern]
+    if digit_group is not None:
+        if name == 'gpt2' or isinstance(digit_group, bool) or digit_group not in (1, 3):
+            raise ValueError("digit_group is 1 or 3 and goes with pattern='cl100k', not {!r} with "
+                             '{!r}'.format(digit_group, pattern))
+        group = digit_group
+    if not isinstance(ignore_merges, bool):
+        raise ValueError('ignore_merges must be a bool, not {!r}'.format(ignore_merges))
+    return name, group, ignore_merges
 
 
 def bytes_to_unicode():
@@ -63,6 +91,80 @@ def load_tables(vocab_json, merges_txt):
     return tokens, vocab, np.asarray(merges, np.int32).reshape(-1, 3)
 
 
+def load_tokenizer_json(path):
+    """A Hugging Face tokenizer.json of a byte-level BPE -> (tokens, vocab, merges, options):
+    load_tables' three, and BpeContext.from_tables' keywords pattern, ignore_merges and added
+    (the added_tokens as content -> id; one outside model.vocab is a token without bytes, so
+    no text reaches it). The pattern is known by its Split regex string, compared exactly."""
+    if not isinstance(path, str) or not os.path.isfile(path):
+        raise FileNotFoundError('tokenizer_json {!r}: a local file is required'.format(path))
+    with open(path, encoding='utf-8') as f:
+        try:
+            js = json.load(f)
+        except ValueError as e:
+            raise ValueError('{}: not JSON ({})'.format(path, e)) from None
+    model = js.get('model') if isinstance(js, dict) else None
+    if not isinstance(model, dict) or model.get('type', 'BPE') != 'BPE' or \
+            not isinstance(model.get('vocab'), dict) or not isinstance(model.get('merges'), list):
+        raise ValueError('{}: no BPE model with vocab and merges'.format(path))
+    pre = js.get('pre_tokenizer') or {}
+    nodes = pre.get('pretokenizers', [pre]) if pre.get('type') == 'Sequence' else [pre]
+    splits = [n for n in nodes if n.get('type') == 'Split']
+    byte_level = [n for n in nodes if n.get('type') == 'ByteLevel']
+    if len(byte_level) != 1 or byte_level[0].get('add_prefix_space') or len(splits) > 1:
+        raise ValueError('{}: not a byte-level pre-tokenizer without a prefix space'.format(path))
+    if splits:
+        rx = splits[0].get('pattern', {}).get('Regex')
+        if rx not in SPLIT_REGEX or byte_level[0].get('use_regex', True):
+            raise ValueError('{}: unknown pre-tokenizer pattern {!r}'.format(path, rx))
+        pattern = SPLIT_REGEX[rx]
+    elif byte_level[0].get('use_regex', True):
+        pattern = 'gpt2'
+    else:
+        raise ValueError('{}: the pre-tokenizer has no pattern'.format(path))
+    vocab = dict(model['vocab'])
+    if not vocab or not all(isinstance(k, str) and isinstance(v, int) and v >= 0 for k, v in vocab.items()) \
+            or len(set(vocab.values())) != len(vocab):
+        raise ValueError('{}: model.vocab is not an object of token -> distinct id'.format(path))
+    added = {}
+    for t in js.get('added_tokens') or []:
+        if vocab.get(t['content'], t['id']) != t['id'] or (t['content'] not in vocab and
+                                                           t['id'] in vocab.values()):
+            raise ValueError('{}: added token {!r} clashes with model.vocab'.format(path, t['content']))
+        added[t['content']] = t['id']
+    u2b = {c: b for b, c in bytes_to_unicode().items()}
+    tokens = [b''] * (max(list(vocab.values()) + list(added.values())) + 1)
+    for t, i in vocab.items():
+        tokens[i] = bytes(u2b[c] for c in t) if all(c in u2b for c in t) else t.encode('utf-8')
+    merges = []
+    for n, m in enumerate(model['merges']):
+        parts = m.split(' ') if isinstance(m, str) else list(m)
+        if len(parts) != 2 or any(p not in vocab for p in parts + [''.join(parts)]):
+            raise ValueError('{} merge {}: {!r} is not two tokens whose join is one'.format(path, n, m))
+        merges.append([vocab[parts[0]], vocab[parts[1]], vocab[parts[0] + parts[1]]])
+    vocab.update(added)
+    return tokens, vocab, np.asarray(merges, np.int32).reshape(-1, 3), dict(
+        pattern=pattern, ignore_merges=bool(model.get('ignore_merges', False)), added=added)
+
+
+def load_bpe_arg(bpe):
+    """The loaders' bpe= -> (tokens, vocab, merges, BpeContext.from_tables' keywords): a
+    tokenizer.json path, (vocab_json, merges_txt), or that pair followed by a dict of pattern,
+    digit_group and ignore_merges."""
+    if isinstance(bpe, str):
+        return load_tokenizer_json(bpe)
+    if not isinstance(bpe, (tuple, list)) or len(bpe) not in (2, 3) or \
+            (len(bpe) == 3 and not isinstance(bpe[2], dict)):
+        raise ValueError('bpe must be (vocab_json, merges_txt), that pair and a dict of keywords, '
+                         'or a tokenizer.json path, not {!r}'.format(bpe))
+    options = dict(bpe[2]) if len(bpe) == 3 else {}
+    unknown = sorted(set(options) - {'pattern', 'digit_group', 'ignore_merges'})
+    if unknown:
+        raise ValueError('bpe keywords are pattern, digit_group and ignore_merges, not {}'.format(unknown))
+    check_options(**options)
+    return load_tables(*bpe[:2]) + (options,)
+
+
 def load_classes(path=CLASSES):
     """The class table lddl_bpe_create takes (include/lddl_amd.h: header, l1, 64-byte pages of
     2-bit classes) from the ranges of assets/bpe_classes.txt (tools/bpe_classes.py) -> uint8
@@ -105,24 +207,40 @@ def create_native(tokens, merges, device, classes=None):
 class BpeContext:
     """A byte-level BPE vocabulary resident in HBM; kernels run on torch's current stream."""
 
-    def __init__(self, vocab_json, merges_txt, device=None):
-        self._attach(*load_tables(vocab_json, merges_txt), device)
+    def __init__(self, vocab_json, merges_txt, device=None, pattern='gpt2', digit_group=None,
+                 ignore_merges=False):
+        """pattern: 'gpt2' (GPT-2, RoBERTa, BART), 'cl100k' (Llama 3, GPT-4, DeepSeek; digits in
+        groups of digit_group = 3) or 'qwen2' (cl100k with digit_group = 1). ignore_merges: a
+        pre-token that is a vocabulary entry is that entry (Llama 3)."""
+        options = check_options(pattern, digit_group, ignore_merges)
+        self._attach(*load_tables(vocab_json, merges_txt), device, options)
 
     @classmethod
-    def from_tables(cls, tokens, merges, device=None, vocab=None):
+    def from_tables(cls, tokens, merges, device=None, vocab=None, pattern='gpt2', digit_group=None,
+                    ignore_merges=False, added=None):
         """A context of tables already in memory (hand-built, or load_tables' with its vocab):
         tokens (bytes by id) and merges [n, 3] of (left, right, merged) ids in rank order, as
-        lddl_bpe_create takes them."""
+        lddl_bpe_create takes them. added: names -> ids that join special_ids."""
+        options = check_options(pattern, digit_group, ignore_merges)
         self = cls.__new__(cls)
         if vocab is None:
             b2u = bytes_to_unicode()
             vocab = {''.join(b2u[b] for b in t): i for i, t in enumerate(tokens)}
-        self._attach(list(tokens), vocab, np.asarray(merges, np.int32).reshape(-1, 3), device)
+        self._attach(list(tokens), vocab, np.asarray(merges, np.int32).reshape(-1, 3), device,
+                     options, added)
         return self
 
-    def _attach(self, tokens, vocab, merges, device):
+    @classmethod
+    def from_tokenizer_json(cls, path, device=None):
+        """A context of a Hugging Face tokenizer.json (load_tokenizer_json)."""
+        tokens, vocab, merges, options = load_tokenizer_json(path)
+        return cls.from_tables(tokens, merges, device, vocab, **options)
+
+    def _attach(self, tokens, vocab, merges, device, options=('gpt2', 0, False), added=None):
         self.tokens, self.vocab, self.merges = tokens, vocab, merges
         self.special_ids = {t: self.vocab.get(t, -1) for t in SPECIALS}
+        self.special_ids.update(added or {})
+        self.pattern, self.digit_group, self.ignore_merges = options
         import ctypes
         import torch
         from ._native import check, lib
@@ -130,6 +248,9 @@ class BpeContext:
             raise RuntimeError('lddl_amd needs a ROCm GPU; there is no CPU fallback')
         self.device = torch.device('cuda', torch.cuda.current_device() if device is None else device)
         self._h = create_native(self.tokens, self.merges, self.device.index)
+        if options != ('gpt2', 0, False):
+            check(lib.lddl_bpe_set_pattern(self._h, self.pattern.encode(), self.digit_group))
+            check(lib.lddl_bpe_set_whole_words(self._h, int(self.ignore_merges)))
         bits, n = ctypes.c_void_p(), ctypes.c_int64()
         check(lib.lddl_bpe_cont_bits(self._h, ctypes.byref(bits), ctypes.byref(n)))
         self.cont_bits = (bits, n.value)  # lddl_bart_denoise_bits' first two arguments

@@ -50,7 +50,8 @@ BUILD_ID_H = os.path.join(CSRC, 'build_id.h')
 # before it keep the flags their kernels were measured with.
 _NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 UNIT_FLAGS = {u: _NO_PACKED_FP32 for u in ('denoise.hip', 'bpe_split.hip', 'bpe_merge.hip',
-                                           'bpe_api.hip', 'blocks_plan.hip',
+                                           'bpe_api.hip', 'bpe_split_cl.hip', 'bpe_whole.hip',
+                                           'blocks_plan.hip',
                                            'blocks_collate.hip', 't5_corrupt.hip',
                                            'unigram_match.hip', 'unigram_viterbi.hip',
                                            'unigram_api.hip', 'unigram_norm.hip',

@@ -34,8 +34,27 @@ inline
   return h ^ (h >> 13);
 }
 
+// One slot of the whole-word table (ignore_merges): the polynomial hash of a token's
+// bytes (h = h * kBpeWordP + byte + 1 mod 2^64, so one prefix scan hashes every word of a tile)
+// -> the token; linear probing; id kBpeEmpty: a free slot. The bytes are token_off's.
+struct alignas(16) BpeWord {
+  uint64_t hash;
+  uint32_t id, len;
+};
+constexpr uint64_t kBpeWordP = 0x9E3779B97F4A7C15ull;
+
+inline
+#ifdef __HIP__
+    __host__ __device__
+#endif
+    uint32_t
+    bpe_word_slot(uint64_t h) {  // the product's high half: the low bits of a polynomial mod 2^64 mix badly
+  return (uint32_t)(((h ^ (h >> 29)) * 0xBF58476D1CE4E5B9ull) >> 32);
+}
+
 // What bpe_tables.cpp makes of the arguments of lddl_bpe_create.
 struct BpeHostTables {
+  std::vector<BpeWord> words;  // tokens of 2 .. kBpeMaxWord bytes; a power of two, at most half full
   std::vector<BpePair> pairs;  // a power of two of slots, at most half of them taken
   int32_t byte_id[256];
   std::vector<uint32_t> cont_bits;  // bit id: the token's bytes do not start with 0x20
@@ -76,10 +95,26 @@ struct BpeWork {
   int64_t* sent_base;  // pieces before sentence s's first
 };
 
+// Kernel-side view of the whole-word table and of the tokens' bytes.
+struct BpeWordTable {
+  const BpeWord* slots;
+  uint32_t mask;
+  const uint8_t* bytes;
+  const int64_t* off;
+};
+
 #ifdef __HIP__
 // bpe_split.hip: clears doc_bits, alive_bits and the long counter (one region, `clear_words`
 // 64-bit words from doc_bits), marks the document starts, writes start_bits.
 hipError_t bpe_launch_split(const BpeTables& T, const BpeWork& W, int64_t clear_words, hipStream_t st);
+// its first two launches alone (the clear and the document starts)
+hipError_t bpe_launch_docs(const BpeWork& W, int64_t clear_words, hipStream_t st);
+// bpe_split_cl.hip: bpe_launch_split for the cl100k pattern with digit groups of 1 or 3;
+// run_tmp: 3 * n_tiles bytes (a tile's run summaries, then its carries)
+hipError_t bpe_launch_split_cl(const BpeTables& T, const BpeWork& W, int64_t clear_words,
+                               int digit_group, uint8_t* run_tmp, hipStream_t st);
+// bpe_whole.hip, after the merges: a pre-token whose bytes are a token becomes that token
+hipError_t bpe_launch_whole(const BpeWordTable& V, const BpeWork& W, hipStream_t st);
 // bpe_merge.hip: sym and alive_bits from text and start_bits (the tile pass, then the long list).
 hipError_t bpe_launch_merge(const BpeTables& T, const BpeWork& W, hipStream_t st);
 

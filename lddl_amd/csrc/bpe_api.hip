@@ -20,6 +20,14 @@ struct lddl_bpe {
   lddl::BpePair* d_pairs = nullptr;
   int32_t* d_byte_id = nullptr;
   uint32_t* d_cont_bits = nullptr;
+  // the pre-tokenizer (digit_group 0: GPT-2's pattern, 1 or 3: cl100k's) and the
+  // whole-word table with the tokens' bytes, read only when `whole` is set
+  int digit_group = 0;
+  bool whole = false;
+  lddl::BpeWord* d_words = nullptr;
+  uint8_t* d_token_bytes = nullptr;
+  int64_t* d_token_off = nullptr;
+  lddl::BpeWordTable words{};
   int64_t n_tokens = 0, n_merges = 0;
   int32_t unicode[3] = {0, 0, 0};
   lddl::DevArena arena;  // the temporaries of lddl_bpe_tokenize
@@ -133,12 +141,26 @@ __global__ void __launch_bounds__(256) bpe_stats_kernel(BpeWork W, unsigned long
   atomicAdd(out + (len <= 64 ? 1 : 2), 1ull);
 }
 
+// the 64-bit words of temporaries the cl100k split takes on top (3 bytes a tile)
+int64_t split_tmp_words(const lddl_bpe* b, int64_t n_tiles) {
+  return b->digit_group ? (3 * n_tiles + 7) / 8 : 0;
+}
+
+hipError_t launch_split(const lddl_bpe* b, const BpeWork& W, int64_t clear_words, uint64_t* tmp,
+                        hipStream_t st) {
+  if (!b->digit_group) return bpe_launch_split(b->tab, W, clear_words, st);
+  return bpe_launch_split_cl(b->tab, W, clear_words, b->digit_group, reinterpret_cast<uint8_t*>(tmp), st);
+}
+
 void release(lddl_bpe* b) {
   (void)hipFree(b->d_l1);
   (void)hipFree(b->d_pages);
   (void)hipFree(b->d_pairs);
   (void)hipFree(b->d_byte_id);
   (void)hipFree(b->d_cont_bits);
+  (void)hipFree(b->d_words);
+  (void)hipFree(b->d_token_bytes);
+  (void)hipFree(b->d_token_off);
   delete b;
 }
 
@@ -170,12 +192,38 @@ extern "C" int lddl_bpe_create(int device, const uint8_t* class_table, int64_t c
   st = st ? st : upload(&b->d_pairs, H.pairs.data(), H.pairs.size() * sizeof(BpePair));
   st = st ? st : upload(&b->d_byte_id, H.byte_id, sizeof(H.byte_id));
   st = st ? st : upload(&b->d_cont_bits, H.cont_bits.data(), H.cont_bits.size() * sizeof(uint32_t));
+  st = st ? st : upload(&b->d_words, H.words.data(), H.words.size() * sizeof(BpeWord));
+  st = st ? st : upload(&b->d_token_bytes, token_bytes, (size_t)token_off[n_tokens]);
+  st = st ? st : upload(&b->d_token_off, token_off, ((size_t)n_tokens + 1) * sizeof(int64_t));
   if (st) {
     release(b);
     return st;
   }
   b->tab = BpeTables{b->d_l1, b->d_pages, b->d_pairs, (uint32_t)H.pairs.size() - 1, b->d_byte_id};
+  b->words = BpeWordTable{b->d_words, (uint32_t)H.words.size() - 1, b->d_token_bytes, b->d_token_off};
   *out = b;
+  return 0;
+}
+
+extern "C" int lddl_bpe_set_pattern(lddl_bpe* b, const char* pattern, int32_t digit_group) {
+  if (!b || !pattern) LDDL_FAIL(-1, "null argument");
+  const std::string p(pattern);
+  if (p == "gpt2") {
+    if (digit_group != 0) LDDL_FAIL(-1, "pattern gpt2 takes digit_group 0, not %d", digit_group);
+  } else if (p == "cl100k") {
+    if (digit_group != 1 && digit_group != 3)
+      LDDL_FAIL(-1, "pattern cl100k takes digit_group 1 or 3, not %d", digit_group);
+  } else {
+    LDDL_FAIL(-1, "unknown pattern '%s': gpt2 or cl100k", pattern);
+  }
+  b->digit_group = digit_group;
+  return 0;
+}
+
+extern "C" int lddl_bpe_set_whole_words(lddl_bpe* b, int32_t on) {
+  if (!b) LDDL_FAIL(-1, "null bpe");
+  if (on != 0 && on != 1) LDDL_FAIL(-1, "on must be 0 or 1, not %d", on);
+  b->whole = on != 0;
   return 0;
 }
 
@@ -229,7 +277,8 @@ extern "C" int lddl_bpe_tokenize(lddl_bpe* b, void* stream, const uint8_t* d_tex
   // start_bits, tile_base, the scan's scratch, sent_base, long_list; then sym
   const int64_t nt = W.n_tiles + 1, scratch = scan_scratch_elems(W.n_tiles);
   const int64_t clear_words = 2 * nt + 1;
-  const int64_t words = clear_words + nt + nt + scratch + (n_sent + 1) + W.long_cap;
+  const int64_t split_tmp = split_tmp_words(b, W.n_tiles);
+  const int64_t words = clear_words + nt + nt + scratch + (n_sent + 1) + W.long_cap + split_tmp;
   ArenaScope tmp(&b->arena, st);
   uint64_t* base;
   if (tmp.take(&base, words)) return -100;
@@ -242,8 +291,9 @@ extern "C" int lddl_bpe_tokenize(lddl_bpe* b, void* stream, const uint8_t* d_tex
   int64_t* scan_tmp = W.tile_base + nt;
   W.sent_base = scan_tmp + scratch;
   W.long_list = W.sent_base + n_sent + 1;
-  LDDL_HIP(bpe_launch_split(b->tab, W, clear_words, st));
+  LDDL_HIP(launch_split(b, W, clear_words, base + words - split_tmp, st));
   LDDL_HIP(bpe_launch_merge(b->tab, W, st));
+  if (b->whole) LDDL_HIP(bpe_launch_whole(b->words, W, st));
   LDDL_HIP(scan_exclusive(TileCount{W.alive_bits}, W.n_tiles, W.tile_base, scan_tmp, st));
   hipLaunchKernelGGL(bpe_sent_base_kernel, dim3((unsigned)(n_sent / 256 + 1)), dim3(256), 0, st, W);
   hipLaunchKernelGGL(bpe_compact_kernel, dim3((unsigned)((W.n_tiles + 3) / 4)), dim3(256), 0, st, W,
@@ -274,11 +324,11 @@ extern "C" int lddl_bpe_pretoken_stats(lddl_bpe* b, void* stream, const uint8_t*
   const int64_t nt = W.n_tiles + 1, clear_words = nt + 3;
   ArenaScope tmp(&b->arena, st);
   uint64_t* base;
-  if (tmp.take(&base, clear_words + nt)) return -100;
+  if (tmp.take(&base, clear_words + nt + split_tmp_words(b, W.n_tiles))) return -100;
   W.doc_bits = base;
   unsigned long long* counters = reinterpret_cast<unsigned long long*>(base + nt);
   W.start_bits = base + clear_words;
-  LDDL_HIP(bpe_launch_split(b->tab, W, clear_words, st));
+  LDDL_HIP(launch_split(b, W, clear_words, base + clear_words + nt, st));
   hipLaunchKernelGGL(bpe_stats_kernel, dim3((unsigned)((W.n_tiles + 255) / 256)), dim3(256), 0, st, W,
                      counters);
   LDDL_HIP(hipGetLastError());

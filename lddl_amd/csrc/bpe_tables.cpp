@@ -45,6 +45,25 @@ int bpe_build_tables(const uint8_t* ct, int64_t ct_len, const uint8_t* tb, const
   for (int b = 0; b < 256; ++b)
     if (out->byte_id[b] < 0) LDDL_FAIL(-1, "the vocabulary has no token for the single byte 0x%02x", b);
 
+  // ---- the whole-word table (ignore_merges): every token of 2 .. kBpeMaxWord bytes by the
+  // hash of its bytes; of tokens with equal bytes the lowest id ----
+  size_t n_words = 0, wslots = 16;
+  for (int64_t i = 0; i < n_tokens; ++i) n_words += off[i + 1] - off[i] >= 2 && off[i + 1] - off[i] <= kBpeMaxWord;
+  while (wslots < 2 * n_words) wslots <<= 1;
+  out->words.assign(wslots, BpeWord{0, kBpeEmpty, 0});
+  for (int64_t i = 0; i < n_tokens; ++i) {
+    const int64_t len = off[i + 1] - off[i];
+    if (len < 2 || len > kBpeMaxWord) continue;
+    uint64_t h = 0;
+    for (int64_t k = 0; k < len; ++k) h = h * kBpeWordP + tb[off[i] + k] + 1;
+    size_t s = bpe_word_slot(h) & (wslots - 1);
+    for (; out->words[s].id != kBpeEmpty; s = (s + 1) & (wslots - 1)) {
+      const BpeWord& e = out->words[s];
+      if (e.hash == h && e.len == (uint32_t)len && !memcmp(tb + off[e.id], tb + off[i], (size_t)len)) break;
+    }
+    if (out->words[s].id == kBpeEmpty) out->words[s] = BpeWord{h, (uint32_t)i, (uint32_t)len};
+  }
+
   // ---- the merges, in rank order ----
   size_t slots = 16;
   while (slots < 2 * (size_t)n_merges) slots <<= 1;

@@ -181,16 +181,14 @@ def validate_args(path=None, vocab_file=None, batch_size=None, max_seq_length=51
                   mask_ratio=0.3, rank=None, world=None, round_bytes=32 << 20, bpe=None,
                   bpe_tables=None, **kw):
     """Every argument error of get_bart_pretrain_data_loader, raised before the GPU is touched.
-    Returns (files, format). bpe_tables: a list that takes the parsed (tokens, vocab, merges)
-    of bpe=, so that the loader does not read the two files again."""
+    Returns (files, format). bpe_tables: a list that takes the parsed (tokens, vocab, merges,
+    keywords) of bpe= (`lddl_amd.bpe.load_bpe_arg`), so that the loader does not read the two files again."""
     shards = shard_files(path)
     if bpe is not None:
-        if not isinstance(bpe, (tuple, list)) or len(bpe) != 2:
-            raise ValueError('bpe must be (vocab_json, merges_txt), not {!r}'.format(bpe))
         if vocab_file is not None:
             raise ValueError('pass vocab_file (WordPiece) or bpe=, not both')
-        from ..bpe import load_tables
-        tables = load_tables(*bpe)
+        from ..bpe import load_bpe_arg
+        tables = load_bpe_arg(bpe)
         if bpe_tables is not None:
             bpe_tables[:] = tables
     elif not isinstance(vocab_file, str) or not os.path.isfile(vocab_file):
@@ -249,7 +247,7 @@ class BartPretrainLoader:
             from ..bpe import BpeContext
             from ..context import ASSETS
             self._bpe = BpeContext.from_tables(self._bpe_tables[0], self._bpe_tables[2],
-                                               vocab=self._bpe_tables[1])
+                                               vocab=self._bpe_tables[1], **self._bpe_tables[3])
         self._ctx = Context(kw['vocab_file'] if self._bpe is None else os.path.join(
             ASSETS, 'vocab_synth_uncased_30522.txt'), do_lower_case=kw['do_lower_case'])
         pp = kw['punkt_params']

@@ -116,12 +116,15 @@ def _vocab_id(ctx, name):
 
 
 def special_ids_of(ctx, special_ids, fim):
-    """(eos, prefix, middle, suffix): special_ids first, then the vocabulary's <|endoftext|>,
-    else </s>, and <fim_prefix>, <fim_middle>, <fim_suffix>; the sentinels only when `fim`. A
-    missing id is a ValueError naming it."""
+    """(eos, prefix, middle, suffix): special_ids first, then the vocabulary's <|endoftext|> or
+    </s> (the larger id where it has both), and only where it has neither <|end_of_text|> (Llama
+    3); <fim_prefix>, <fim_middle>, <fim_suffix>, the sentinels only when `fim`. A missing id is
+    a ValueError naming it."""
     sp = dict(special_ids or {})
     eos = sp['eos_id'] if 'eos_id' in sp else max(_vocab_id(ctx, '<|endoftext|>'),
                                                    _vocab_id(ctx, '</s>'))
+    if eos < 0 and 'eos_id' not in sp:
+        eos = _vocab_id(ctx, '<|end_of_text|>')
     if eos < 0:
         raise ValueError('the vocab has neither <|endoftext|> nor </s>: pass special_ids '
                          'with eos_id')
@@ -214,7 +217,7 @@ class GptPretrainLoader(RobertaPretrainLoader):
                                                   normalizer=(keys, repls) if keys else None)
         else:
             self.bpe = BpeContext.from_tables(self._bpe_tables[0], self._bpe_tables[2],
-                                              vocab=self._bpe_tables[1])
+                                              vocab=self._bpe_tables[1], **self._bpe_tables[3])
         self._ctx = self.bpe  # no Punkt pass: the tokenizer's context is the device's owner
         self.seed = mix_seed(kw['base_seed'], self.rank)
         special_ids_of(self.bpe, kw['special_ids'], kw['fim_rate'] > 0)  # missing ids, up front
@@ -288,8 +291,10 @@ def get_gpt_pretrain_data_loader(path, bpe=None, unigram=None, batch_size=None,
     """GPT pretraining batches from the text files (*.txt, one document per line) under `path`
     (past the reference, which has no GPT loader). get_roberta_pretrain_data_loader's
     rounds and ranks; a line is a document of one sentence (no Punkt pass), tokenized whole by
-    BpeContext.tokenize of bpe=(vocab_json, merges_txt), or by the unigram model of
-    unigram=model_file, so its ids are `encode(line)`. Per epoch and round a seeded permutation
+    BpeContext.tokenize of bpe=(vocab_json, merges_txt), of that pair and a dict of BpeContext's
+    pattern / digit_group / ignore_merges, or of bpe=tokenizer_json (Llama 3, GPT-4, Qwen2:
+    DESIGN §35), or by the unigram model of unigram=model_file, so its ids are `encode(line)`
+    (as are, with bpe=, those of the RoBERTa, T5 and BART loaders). Per epoch and round a seeded permutation
     orders the documents in the stream (shuffle_docs=False keeps the files' order), stream_plan
     packs them across rows of max_seq_length slots with fim=(fim_rate, fim_spm_rate, the rank's
     seed, epoch), n_rows is the round's one sync, a second seeded permutation cuts the rows into

@@ -160,7 +160,8 @@ def validate_args(path=None, bpe=None, batch_size=None, max_seq_length=512, mode
                   world=None, round_bytes=32 << 20, special_ids=None, bpe_tables=None,
                   unigram=None, unigram_tables=None, **kw):
     """Every argument error of get_roberta_pretrain_data_loader, raised before the GPU is
-    touched. Returns the files. bpe_tables takes the parsed (tokens, vocab, merges) of bpe=,
+    touched. Returns the files. bpe_tables takes the parsed (tokens, vocab, merges, keywords) of bpe=
+    (`lddl_amd.bpe.load_bpe_arg`: the two files, the two and a dict, or a tokenizer.json),
     unigram_tables what `lddl_amd.unigram.load_model` reads from unigram=."""
     files = text_files(path)
     if unigram is not None:
@@ -171,10 +172,8 @@ def validate_args(path=None, bpe=None, batch_size=None, max_seq_length=512, mode
         if unigram_tables is not None:
             unigram_tables[:] = tables
     else:
-        if not isinstance(bpe, (tuple, list)) or len(bpe) != 2:
-            raise ValueError('bpe must be (vocab_json, merges_txt), not {!r}'.format(bpe))
-        from ..bpe import load_tables
-        tables = load_tables(*bpe)
+        from ..bpe import load_bpe_arg
+        tables = load_bpe_arg(bpe)
         if bpe_tables is not None:
             bpe_tables[:] = tables
     if not isinstance(batch_size, int) or isinstance(batch_size, bool) or batch_size < 1:
@@ -221,7 +220,7 @@ class RobertaPretrainLoader:
                                                   normalizer=(keys, repls) if keys else None)
         else:
             self.bpe = BpeContext.from_tables(self._bpe_tables[0], self._bpe_tables[2],
-                                              vocab=self._bpe_tables[1])
+                                              vocab=self._bpe_tables[1], **self._bpe_tables[3])
         # Punkt's tables live in a Context of the packaged WordPiece vocabulary, which here only
         # segments (as in the BART loader with bpe=)
         self._ctx = Context(os.path.join(ASSETS, 'vocab_synth_uncased_30522.txt'))
